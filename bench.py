@@ -2,7 +2,7 @@
 """images/sec, forward+backward(+Adam), UniPose ResNet-101 on synthetic 368x368 batches (BASELINE.json
 configs[1]: K=16, batch 32/GPU, fp32) on N MI355X of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,10 @@ One process per GPU (RCCL via torch.distributed "nccl"); the batch is sharded (w
 images per GPU), weights are replicated, gradients are all-reduced once per step (unipose_amd/dist.py).
 A step = zero_grad -> forward -> MSE -> backward -> gradient all-reduce -> Adam, exactly the loop of
 the reference's Trainer.training (unipose.py:100-131) with synthetic inputs already resident in HBM.
-Rank 0 prints ONE JSON line.  `roofline` is measured live: on every 5th step of the timed region each
+Rank 0 prints ONE JSON line.  A plain run sets up, settles and warms up, times K steps (`ms_per_step`),
+writes the last step's outputs if --dump-outputs is given (dump_outputs) and prints the line; nothing else.
+--full adds the extras below (and `alt_math`, `other_configs`, the WASP leg), each after the timed region.
+`roofline` (--full) is measured live: on every 5th step of the timed region each
 MFMA convolution launch is bracketed by hipEvents on its stream (up_profile_begin/enable/end in the C ABI).
 `cpu_baseline` times the CPU oracle (a torch-CPU restatement of the reference graph, pinned to the
 reference by tests/golden) on this box's host cores on a bounded sample; `stock_gpu_baseline` times the same graph on
@@ -213,11 +216,13 @@ def wasp_dilated_leg(dev, batch=32, hw=23, iters=20, bf16=False, dilations=(6, 1
 HBM_PEAK_TBPS = 8.0
 
 
-def make_workload(dev, lstm, K, B, S, T, seed, emu=False, init=None, graph=False):
+def make_workload(dev, lstm, K, B, S, T, seed, emu=False, init=None, graph=False, record=None):
     """Model + resident synthetic batch + the train step of the reference's loops (unipose.py:100-131 /
     uniposeLSTM.py:116-133).  Returns (model, optimizer, step(reducer=None)).
     init (tests: the G16 trajectory fixture drives THIS step function): {"state_dict", "x", "t"} replace the random
-    initialisation and batch of the image model, "no_dropout" sets the three dropouts to p = 0."""
+    initialisation and batch of the image model, "no_dropout" sets the three dropouts to p = 0.
+    record (--dump-outputs): a dict in which every eager step leaves its forward's heat maps under "heatmaps" (a list, one per
+    frame for the video model); None keeps no reference."""
     from unipose_amd import ops
     g = torch.Generator(device="cpu").manual_seed(seed)
     if lstm:
@@ -264,11 +269,16 @@ def make_workload(dev, lstm, K, B, S, T, seed, emu=False, init=None, graph=False
             cell = torch.zeros(K + 2, hs, hs, device=dev)
             hide = torch.zeros(K + 2, hs, hs, device=dev)
             loss = 0.0
+            heats = []
             for j in range(T):
                 heat, cell, hide = model(x, cm, j, heat, hide, cell)
+                heats.append(heat)
                 loss = loss + ops.mse_loss(heat, t[:, j])
         else:
-            loss = ops.mse_loss(model(x), t)
+            heats = [model(x)]
+            loss = ops.mse_loss(heats[0], t)
+        if record is not None:
+            record["heatmaps"] = [h.detach() for h in heats]
         if lstm:
             with ops.deferred_wgrad():                         # every weight is used T times: see ops.deferred_wgrad
                 loss.backward()
@@ -279,6 +289,52 @@ def make_workload(dev, lstm, K, B, S, T, seed, emu=False, init=None, graph=False
         opt.step()
         return loss
     return model, opt, step
+
+
+DUMP_SAMPLE = 1 << 21               # --dump-outputs: elements kept of the weights / of their gradients (8 MB each in fp32)
+DUMP_HEATMAP_MAX = 1 << 23          # ... and at most this many of the heat maps (32 MB); the whole dump stays below 64 MB
+
+
+def _seeded_sample(flat, n, seed):
+    """A fixed sample of a 1-D tensor: n indices drawn from a CPU generator seeded with `seed`, sorted; the whole tensor if
+    it has at most n elements.  Depends on the size of `flat` only, so two builds sample the same positions."""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, loss, model, record):
+    """--dump-outputs DIR: what the timed path's last step handed its caller, written as DIR/<name>.npy so that two builds run
+    with the same arguments (identical seeded inputs and weights) can be compared output for output:
+      loss.npy            float64 [1]      the step's loss (the video model: summed over the frames)
+      heatmaps.npy        float32          the forward's heat maps, [B, K+1, H/8, W/8] ([B, T, K+1, H/8, W/8] for the video
+                                           model; a seeded sample of DUMP_HEATMAP_MAX elements when larger; absent for --graph)
+      weights_sample.npy  float32 [2^21]   the parameters after the optimizer step, all of them flattened in
+                                           model.parameters() order, sampled at seeded positions (seed 1)
+      grads_sample.npy    float32 [2^21]   their gradients at the same positions (zeros where a parameter has none)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {"loss": np.asarray([float(loss.detach())], dtype=np.float64)}
+    heats = (record or {}).get("heatmaps")
+    if heats:
+        h = torch.stack(heats, 1) if len(heats) > 1 else heats[0]
+        h = h.float()
+        if h.numel() > DUMP_HEATMAP_MAX:
+            h = _seeded_sample(h.reshape(-1), DUMP_HEATMAP_MAX, 2)
+        out["heatmaps"] = h.cpu().numpy()
+    params = list(model.parameters())
+    with torch.no_grad():
+        w = torch.cat([p.detach().reshape(-1).float() for p in params])
+        out["weights_sample"] = _seeded_sample(w, DUMP_SAMPLE, 1).cpu().numpy()
+        del w
+        g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        out["grads_sample"] = _seeded_sample(g, DUMP_SAMPLE, 1).cpu().numpy()
+        del g
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in out.items()}
 
 
 def profile_rows(lib, steps_profiled=1):
@@ -448,7 +504,20 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=min(os.cpu_count() or 1, 64),
                     help="host threads for the CPU baseline (default: min(cores, 64); more oversubscribes oneDNN)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-launch roofline of the timed region and its exclusive "
+                         "pass, WASP dilated leg, split-bf16 alt-math loop, other BASELINE configs, stock GPU and CPU "
+                         "baselines (each still switched off by its --no-* option).  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, heat maps, seeded samples of the "
+                         "updated weights and their gradients) as DIR/<name>.npy, float32 / float64, < 64 MB (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:           # a plain run: the headline figure only
+        args.no_profile = args.no_alt_math = args.no_other_configs = True
+        args.no_stock_baseline = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -526,7 +595,9 @@ def main():
     if args.graph:          # the capture fixes the arithmetic: set it first; per-launch events cannot ride in a replay
         ops.set_conv_math(args.math)
         args.no_profile = True
-    model, opt, step1 = make_workload(dev, lstm, K, B, S, T, seed=shard_seed(0, rank), emu=emu, graph=args.graph)
+    record = {} if args.dump_outputs and rank == 0 else None
+    model, opt, step1 = make_workload(dev, lstm, K, B, S, T, seed=shard_seed(0, rank), emu=emu, graph=args.graph,
+                                      record=record)
     ops.manual_seed(shard_seed(0, rank))
     ops.set_conv_math(args.math)
     # default: ONE flat all-reduce after backward (190 MB: ~1-2 ms on xGMI against a 66 ms fp32 step); --overlap: 32 MB
@@ -600,6 +671,9 @@ def main():
     xch["on"] = False
     log(f"timed region: {args.steps} steps in {dt:.3f}s")
     loss_val = float(loss.detach())
+    if record is not None:      # before anything else runs a step: the timed path's last results
+        shapes = dump_outputs(args.dump_outputs, loss, model, record)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
     dp = None
     if use_dist:
         # first-run proof for N > 1: every rank's own clock, the exchange's share, and whether the replicas still agree

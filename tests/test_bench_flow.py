@@ -20,12 +20,13 @@ def _free_port():
     return p
 
 
-def _run(nproc, extra=(), plain=False, emu_threads=4, timeout=900):
+def _run(nproc, extra=(), plain=False, emu_threads=4, timeout=900, full=True):
     env = dict(os.environ, UP_EMU_THREADS=str(emu_threads), OMP_NUM_THREADS="2" if nproc <= 2 else "1")
     # the emulator needs ~10-20 s per training step of the full ResNet-101: no warm-up, one timed step (plus the two of the
-    # exclusive pass), no alt-math loop (that loop has no rank-dependent branch)
+    # exclusive pass), no alt-math loop (that loop has no rank-dependent branch).  full: the --full control flow (exclusive
+    # pass, baselines); without it the plain run (headline only)
     args = ["--gpus", str(nproc), "--steps", "1", "--warmup", "0", "--batch", "2", "--size", "32", "--dry-run-emu",
-            "--no-alt-math", *extra]     # (a later --steps in `extra` wins)
+            "--no-alt-math", *(["--full"] if full else []), *extra]     # (a later --steps in `extra` wins)
     if nproc == 1 or plain:           # plain: no launcher, bench.py starts its own ranks (bench.self_launch)
         env.pop("WORLD_SIZE", None)
         cmd = [sys.executable, "bench.py", *args]
@@ -69,6 +70,32 @@ def test_bench_flow_single_rank_contract():
     assert out["warmup"] == 0 and out["n_gpus"] == 1 and out["scaling"] == "weak" and out["higher_is_better"] is True
     assert out["vs_baseline"] is None and out["dtype"] == "f32" and out["data"] == "synthetic"
     assert set(out["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"} and out["cpu_baseline"]["kind"] == "port"
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline line without the extras; --dump-outputs writes the
+    last timed step's results as float32 / float64 .npy files below 64 MB, and a second run with the same arguments writes
+    the same arrays (seeded inputs, weights and samples)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = _run(1, ["--steps", "2", "--dump-outputs", str(d)], full=False)
+        assert out["steps"] == 2 and out["warmup"] == 0 and out["n_gpus"] == 1 and out["higher_is_better"] is True
+        assert out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["unit"] == "images/sec"
+        for key in ("cpu_baseline", "roofline", "alt_math", "other_configs", "stock_gpu_baseline"):
+            assert key not in out, key
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["grads_sample.npy", "heatmaps.npy", "loss.npy", "weights_sample.npy"], files
+        assert sum(p.stat().st_size for p in d.iterdir()) < 64 << 20
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["heatmaps"].shape == (2, 17, 4, 4)
+        assert float(arrs["loss"][0]) == out["loss"]
+        assert np.isfinite(arrs["grads_sample"]).all() and np.abs(arrs["grads_sample"]).max() > 0
+        dumps.append(arrs)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
 
 
 def test_bench_flow_four_ranks_overlapped_buckets():
