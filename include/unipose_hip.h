@@ -40,7 +40,8 @@ typedef enum {
 } up_status;
 
 const char* up_last_error(void);
-int up_abi_version(void);   /* 10 */
+int up_abi_version(void);   /* 10; the revision that added the up_clip_* layout kernels and the up_unipose_lstm_* video entry
+                               points kept it at 10: the additions are purely additive */
 
 /* Geometry of one 2-D convolution (nn.Conv2d as used at resnet.py:10-16,61,80-84,104-109;
  * wasp.py:9,52,59-60; decoder.py:17,22,26,30; model/uniposeLSTM.py:12-14,30-38,85-89). */
@@ -392,6 +393,16 @@ int up_gap_bwd(const float* dy, float* dx, int lddx, int N, int HW, int C, void*
 /* nn.AvgPool2d(9,8,1) on the 1-channel centre map (model/uniposeLSTM.py:75,114); NCHW(1ch) in,
  * writes channel `coff` of an NHWC buffer with pixel stride ldy */
 int up_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int N, int H, int W, int P, int Q, void* stream);
+/* Clip layout (ABI 10 additions, the video plan below): a clip is batch-major, (B, T, ...); the trunk and the head of the video
+ * network run frame-major, on T * B images, image f = t * B + b.  Data movement only (the pooling is avgpool9s8's arithmetic):
+ *   up_clip_nchw_to_nhwc    x (B, T, C, H, W) -> y frame-major (T * B, H, W, ldy), pad channels C <= c < ldy zero
+ *   up_clip_avgpool9s8_fwd  AvgPool2d(9,8,1) of the (B, T, 1, H, W) centre maps into channel coff of the frame-major
+ *                           (T * B, P, Q, ldy) buffer
+ *   up_clip_nhwc_to_nchw    x frame-major (T * B, H, W, ldx) -> y (B, T, C, H, W)
+ * ldy / ldx % 4 == 0 and a 16-byte aligned NHWC pointer. */
+int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream);
+int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q, void* stream);
+int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream);
 /* nn.Dropout (wasp.py:63, decoder.py:25,29): keep-mask from a counter hash of (seed, element index)
  * or, when ext_mask != NULL, from the caller (float 0/1) — the injectable-RNG hook used for parity. */
 int up_dropout_fwd(const float* x, float* y, uint8_t* mask, const float* ext_mask, int64_t n,
@@ -505,6 +516,41 @@ int up_unipose_plan_set_conv(up_unipose_plan* plan, int i, const float* w_oihw, 
 size_t up_unipose_plan_workspace(const up_unipose_plan* plan);
 int up_unipose_forward(up_unipose_plan* plan, const float* x_nchw, float* heat_nchw, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ---- whole-clip and per-frame inference entry of UniPose-LSTM (ABI 10 additions) ----------------------------------------
+ * The video network (model/uniposeLSTM.py:67-138: the image trunk with the video WASP, ConvLSTM, five-convolution head) with
+ * every BatchNorm folded, like up_unipose_forward above: the plan owns the packed weights, activations and the recurrent state
+ * between frames live in a caller-provided workspace of up_unipose_lstm_plan_workspace() bytes (256-byte aligned).  Two forms:
+ *   up_unipose_lstm_step  one frame, what the reference's loop issues as `heat, cell, hide = model(x, cm, j, heat, hide, cell)`
+ *                         (uniposeLSTM.py:124-128): x (B, 3, H, W), centre map (B, 1, H, W), the caller's state prev_hide /
+ *                         prev_cell (B, K+2, h, w) NCHW, both NULL for the first frame (LSTM_0); writes heat (B, K+1, h, w) and
+ *                         the new cell / hide (B, K+2, h, w).  Launches of the drop-in module's per-frame path.
+ *   up_unipose_lstm_clip  the whole clip of config.frames frames: x (B, T, 3, H, W), centre maps (B, T, 1, H, W) -> heat
+ *                         (B, T, K+1, h, w) and the cell / hide of the LAST frame (either may be NULL).  The trunk once on the T * B
+ *                         frames, the recurrence frame by frame with the state kept in the workspace, the head once on the T * B
+ *                         hidden states: the launches of the module's whole-clip unroll (batch_frames).
+ * h = ceil(H / 8) must equal the pooled centre map's (H - 7) / 8 + 1, i.e. H % 8 (and W % 8) in {0, 7}: create refuses the rest.
+ * Convolution names are the reference's state_dict prefixes: the trunk's (wasp.conv2 twice; the video WASP's
+ * wasp.global_avg_pool.1 has no bias), lstm_0.conv_{g,i,o}_lstm, lstm.conv_{g,i,o,f}{x,h}_lstm and conv1 .. conv5.  The plan
+ * stacks the gate weights itself once all parts of a cell are set; a forward call while any is unset fails ("never set"). */
+typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
+typedef struct {
+    int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */
+    int32_t output_stride;                  /* 16 or 8 */
+    int32_t num_classes;                    /* K: heat-maps K+1, recurrent state K+2 channels */
+} up_unipose_lstm_config;
+int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** plan);
+void up_unipose_lstm_plan_destroy(up_unipose_lstm_plan* plan);
+int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* plan);
+const char* up_unipose_lstm_plan_conv_name(const up_unipose_lstm_plan* plan, int i);
+int up_unipose_lstm_plan_conv_shape(const up_unipose_lstm_plan* plan, int i, int32_t* oihw /* [4] */, int32_t* has_bias);
+int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* plan, int i, const float* w_oihw, const float* bias, void* stream);
+size_t up_unipose_lstm_plan_workspace(const up_unipose_lstm_plan* plan);
+int up_unipose_lstm_step(up_unipose_lstm_plan* plan, const float* x_nchw, const float* center_nchw, const float* prev_hide,
+                         const float* prev_cell, float* heat_nchw, float* cell_nchw, float* hide_nchw, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int up_unipose_lstm_clip(up_unipose_lstm_plan* plan, const float* x, const float* center, float* heat, float* cell_last,
+                         float* hide_last, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg; no reference counterpart) ----
  * Between begin/end every MFMA convolution launch is bracketed by two hipEvents on its stream;

@@ -156,6 +156,18 @@ SIGNATURES = {
     "up_unipose_plan_set_conv": (_i, [_p, _i, _p, _p, _p]),
     "up_unipose_plan_workspace": (_sz, [_p]),
     "up_unipose_forward": (_i, [_p, _p, _p, _p, _sz, _p]),
+    "up_clip_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "up_unipose_lstm_plan_create": (_i, [_p, C.POINTER(_p)]),
+    "up_unipose_lstm_plan_destroy": (None, [_p]),
+    "up_unipose_lstm_plan_num_convs": (_i, [_p]),
+    "up_unipose_lstm_plan_conv_name": (C.c_char_p, [_p, _i]),
+    "up_unipose_lstm_plan_conv_shape": (_i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "up_unipose_lstm_plan_set_conv": (_i, [_p, _i, _p, _p, _p]),
+    "up_unipose_lstm_plan_workspace": (_sz, [_p]),
+    "up_unipose_lstm_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_lstm_clip": (_i, [_p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "up_profile_variants": (_i, []),
     "up_profile_variant_name": (C.c_char_p, [_i]),
     "up_profile_begin": (_i, []),

@@ -11,6 +11,10 @@
 // The launches, their order, their descriptors and their epilogues are exactly those of the drop-in module's folded inference
 // forward (unipose_amd/unipose.py + modules.py after checkpoint.load_folded), so the two produce equal bits
 // (tests/test_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
+//
+// The video network UniPose-LSTM (model/uniposeLSTM.py) has its entry here too (up_unipose_lstm_*, ABI 10 additions): the same
+// trunk builder with the video WASP, then the centre-map hand-over, the ConvLSTM cell and the head — per frame with the caller's
+// state (the module's per-frame path) or for a whole clip (its batch_frames unroll), equal bits again (tests/test_lstm_plan_*.py).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -62,21 +66,26 @@ struct Conv {
     float* bias = nullptr;
     bool set = false;
 };
-enum Kind { TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW };
+enum Kind {
+    TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW,
+    // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
+    POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL
+};
+enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
 struct Op {
     Kind kind;
-    Ref in, out, res;
+    Ref in, out, res, aux;
     int conv = -1;
+    int n = 0;                        // images the op runs on (batch, or T * batch in the clip's trunk and head)
+    Ext ext = X;                      // TO_NHWC / TO_NCHW / POOL and their clip forms: the caller's tensor
     int a = 0, b = 0, c = 0, e = 0;   // kind-specific integers (see run)
 };
 
 struct Plan {
-    up_unipose_config cfg;
     std::vector<Tensor> tensors;
     std::vector<Conv> convs;
     std::vector<Op> ops;
     size_t ws_bytes = 0;
-    int input_id = -1;
 
     int tensor(int n, int h, int w, int c, size_t elem = 4) {
         Tensor t;
@@ -96,6 +105,7 @@ struct Plan {
         touch(op.in);
         touch(op.out);
         touch(op.res);
+        touch(op.aux);
         ops.push_back(op);
     }
     // conv (+ folded-BatchNorm bias) (+ residual) (+ ReLU) of `images` images at (h, w) with cp physical input channels
@@ -122,6 +132,62 @@ struct Plan {
         push(op);
         return out;
     }
+    void zero(Ref t) {
+        Op op;
+        op.kind = ZERO;
+        op.out = t;
+        push(op);
+    }
+    void copy(Ref src, int lds, Ref dst, int ldd, size_t dst_ch, long long rows, int ch) {
+        Op op;
+        op.kind = COPY;
+        op.in = src; op.out = dst;
+        op.out.elems += dst_ch;
+        op.a = lds; op.b = ldd; op.c = ch; op.e = (int)rows;
+        push(op);
+    }
+    // workspace layout: first fit over the live ranges, buffers of dead tensors are reused
+    void layout() {
+        struct Block {
+            size_t off, bytes;
+        };
+        std::vector<Block> free_list;
+        size_t top = 0;
+        for (int i = 0; i < (int)ops.size(); ++i) {
+            for (int t = 0; t < (int)tensors.size(); ++t) {
+                Tensor& T = tensors[t];
+                if (T.first != i) continue;
+                bool placed = false;
+                for (size_t f = 0; f < free_list.size(); ++f)
+                    if (free_list[f].bytes >= T.bytes) {
+                        T.off = free_list[f].off;
+                        free_list[f].off += T.bytes;
+                        free_list[f].bytes -= T.bytes;
+                        placed = true;
+                        break;
+                    }
+                if (!placed) {
+                    T.off = top;
+                    top += T.bytes;
+                }
+            }
+            for (int t = 0; t < (int)tensors.size(); ++t) {
+                Tensor& T = tensors[t];
+                if (T.last != i) continue;
+                free_list.push_back({T.off, T.bytes});
+                // merge neighbours
+                std::sort(free_list.begin(), free_list.end(), [](const Block& a, const Block& b) { return a.off < b.off; });
+                std::vector<Block> merged;
+                for (const Block& b : free_list) {
+                    if (b.bytes == 0) continue;
+                    if (!merged.empty() && merged.back().off + merged.back().bytes == b.off) merged.back().bytes += b.bytes;
+                    else merged.push_back(b);
+                }
+                free_list.swap(merged);
+            }
+        }
+        ws_bytes = top;
+    }
 };
 
 // resnet.py:5-42 — conv1 / conv2 / conv3 (+ downsample) of one Bottleneck, BatchNorm folded, the residual add and the last ReLU in
@@ -139,12 +205,14 @@ static Ref bottleneck(Plan& p, const std::string& name, Ref x, int n, int& h, in
     return out;
 }
 
-static int build(Plan& p) {
-    const up_unipose_config& c = p.cfg;
-    const int n = c.batch;
-    int h = c.height, w = c.width;
+// The trunk both plans share: ResNet-101 + WASP + decoder on `n` NHWC images `x` (4 channels) of h x w, BatchNorm folded.  Returns
+// decoder.last_conv.8's output (n, h/8, w/8, rup4(out_channels)) NHWC; `h` / `w` become its size.  video: the WASP of
+// waspVideo.py:56-59, whose global-average-pool branch has no BatchNorm (a convolution without bias), and the heat-map tensor
+// zeroed before the last convolution writes it: its spare pad channel is where the centre map goes (uniposeLSTM.py _AddCenter),
+// and the ConvLSTM gate convolution reads every physical channel.
+static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int out_channels, bool video) {
     int strides[4], dils[4];
-    if (c.output_stride == 16) {
+    if (output_stride == 16) {
         const int s[4] = {1, 2, 2, 1}, d[4] = {1, 1, 1, 2};
         memcpy(strides, s, sizeof(s));
         memcpy(dils, d, sizeof(d));
@@ -152,15 +220,6 @@ static int build(Plan& p) {
         const int s[4] = {1, 2, 1, 1}, d[4] = {1, 1, 2, 4};
         memcpy(strides, s, sizeof(s));
         memcpy(dils, d, sizeof(d));
-    }
-    // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC)
-    Ref x;
-    x.id = p.tensor(n, h, w, 4);
-    {
-        Op op;
-        op.kind = TO_NHWC;
-        op.out = x;
-        p.push(op);
     }
     // stem: 7x7 s2 + folded bn1 + ReLU, 3x3 s2 max-pool (resnet.py:113-117)
     x = p.conv("backbone.conv1", x, n, h, w, 4, 3, 64, 7, 2, 3, 1, 1, true);
@@ -174,6 +233,7 @@ static int build(Plan& p) {
         Op op;
         op.kind = MAXPOOL;
         op.in = in; op.out = out; op.res = idx;
+        op.n = n;
         op.a = hh; op.b = ww; op.c = ch;
         p.push(op);
         return out;
@@ -203,8 +263,8 @@ static int build(Plan& p) {
     }
     // WASP (wasp.py:66-90; modules.WASP.forward): the four branch outputs are rows of ONE (4N, h, w, 256) tensor, so that the
     // twice-applied 1x1 convolution runs as two launches over 4 N h w rows
-    const int wd[4] = {c.output_stride == 16 ? 24 : 48, c.output_stride == 16 ? 18 : 36, c.output_stride == 16 ? 12 : 24,
-                       c.output_stride == 16 ? 6 : 12};
+    const int wd[4] = {output_stride == 16 ? 24 : 48, output_stride == 16 ? 18 : 36, output_stride == 16 ? 12 : 24,
+                       output_stride == 16 ? 6 : 12};
     Ref stack;
     stack.id = p.tensor(4 * n, h, w, 256);
     const size_t branch = (size_t)n * h * w * 256;
@@ -225,16 +285,18 @@ static int build(Plan& p) {
         Op op;
         op.kind = GAP;
         op.in = x; op.out = g;
+        op.n = n;
         op.a = h * w; op.c = 2048;
         p.push(op);
     }
-    g = p.conv("wasp.global_avg_pool.1", g, n, 1, 1, 2048, 2048, 256, 1, 1, 0, 1, 1, true);
+    g = p.conv("wasp.global_avg_pool.1", g, n, 1, 1, 2048, 2048, 256, 1, 1, 0, 1, 1, !video);
     auto bilinear = [&](Ref in, int hh, int ww, int ch, int ph, int pw) {
         Ref out;
         out.id = p.tensor(n, ph, pw, ch);
         Op op;
         op.kind = BILINEAR;
         op.in = in; op.out = out;
+        op.n = n;
         op.a = hh; op.b = ww; op.c = ch; op.e = ph * 65536 + pw;
         p.push(op);
         return out;
@@ -242,20 +304,12 @@ static int build(Plan& p) {
     g = bilinear(g, 1, 1, 256, h, w);
     Ref cat;
     cat.id = p.tensor(n, h, w, 1280);
-    auto copy = [&](Ref src, int lds, Ref dst, int ldd, size_t dst_ch, long long rows, int ch) {
-        Op op;
-        op.kind = COPY;
-        op.in = src; op.out = dst;
-        op.out.elems += dst_ch;
-        op.a = lds; op.b = ldd; op.c = ch; op.e = (int)rows;
-        p.push(op);
-    };
     for (int i = 0; i < 4; ++i) {
         Ref s = y;
         s.elems = i * branch;
-        copy(s, 256, cat, 1280, (size_t)i * 256, (long long)n * h * w, 256);
+        p.copy(s, 256, cat, 1280, (size_t)i * 256, (long long)n * h * w, 256);
     }
-    copy(g, 256, cat, 1280, 1024, (long long)n * h * w, 256);
+    p.copy(g, 256, cat, 1280, 1024, (long long)n * h * w, 256);
     x = p.conv("wasp.conv1", cat, n, h, w, 1280, 1280, 256, 1, 1, 0, 1, 1, true);   // + folded bn1 + ReLU; dropout is the identity in eval
     // decoder (decoder.py:38-56)
     Ref lw = p.conv("decoder.conv1", low, n, low_h, low_w, 256, 256, 48, 1, 1, 0, 1, 1, true);
@@ -264,64 +318,240 @@ static int build(Plan& p) {
     x = bilinear(x, h, w, 256, dh, dw);
     Ref cat2;
     cat2.id = p.tensor(n, dh, dw, 320);      // 256 + 48 = 304 real channels, zero-padded to a multiple of 32
-    {
-        Op op;
-        op.kind = ZERO;
-        op.out = cat2;
-        p.push(op);
-    }
-    copy(x, 256, cat2, 320, 0, (long long)n * dh * dw, 256);
-    copy(lw, 48, cat2, 320, 256, (long long)n * dh * dw, 48);
+    p.zero(cat2);
+    p.copy(x, 256, cat2, 320, 0, (long long)n * dh * dw, 256);
+    p.copy(lw, 48, cat2, 320, 256, (long long)n * dh * dw, 48);
     x = p.conv("decoder.last_conv.0", cat2, n, dh, dw, 320, 304, 256, 3, 1, 1, 1, 1, true);
     x = p.conv("decoder.last_conv.4", x, n, dh, dw, 256, 256, 256, 3, 1, 1, 1, 1, true);
-    x = p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, c.out_channels, 1, 1, 0, 1, 0, true);
+    Ref heat;
+    if (video && rup4(out_channels) != out_channels) {
+        heat.id = p.tensor(n, dh, dw, rup4(out_channels));
+        p.zero(heat);
+    }
+    h = dh;
+    w = dw;
+    return p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, out_channels, 1, 1, 0, 1, 0, true, Ref(), heat);
+}
+
+static int build(Plan& p, const up_unipose_config& c) {
+    const int n = c.batch;
+    int h = c.height, w = c.width;
+    // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC)
+    Ref x;
+    x.id = p.tensor(n, h, w, 4);
+    {
+        Op op;
+        op.kind = TO_NHWC;
+        op.out = x;
+        op.ext = X;
+        op.n = n; op.c = 3;
+        p.push(op);
+    }
+    x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
     {
         Op op;
         op.kind = TO_NCHW;
         op.in = x;
-        op.a = dh; op.b = dw; op.c = c.out_channels; op.e = rup4(c.out_channels);
+        op.ext = HEAT;
+        op.n = n; op.c = c.out_channels;
         p.push(op);
     }
-    // workspace layout: first fit over the live ranges, buffers of dead tensors are reused
-    struct Block {
-        size_t off, bytes;
-    };
-    std::vector<Block> free_list;
-    size_t top = 0;
-    for (int i = 0; i < (int)p.ops.size(); ++i) {
-        for (int t = 0; t < (int)p.tensors.size(); ++t) {
-            Tensor& T = p.tensors[t];
-            if (T.first != i) continue;
-            bool placed = false;
-            for (size_t f = 0; f < free_list.size(); ++f)
-                if (free_list[f].bytes >= T.bytes) {
-                    T.off = free_list[f].off;
-                    free_list[f].off += T.bytes;
-                    free_list[f].bytes -= T.bytes;
-                    placed = true;
-                    break;
-                }
-            if (!placed) {
-                T.off = top;
-                top += T.bytes;
-            }
-        }
-        for (int t = 0; t < (int)p.tensors.size(); ++t) {
-            Tensor& T = p.tensors[t];
-            if (T.last != i) continue;
-            free_list.push_back({T.off, T.bytes});
-            // merge neighbours
-            std::sort(free_list.begin(), free_list.end(), [](const Block& a, const Block& b) { return a.off < b.off; });
-            std::vector<Block> merged;
-            for (const Block& b : free_list) {
-                if (b.bytes == 0) continue;
-                if (!merged.empty() && merged.back().off + merged.back().bytes == b.off) merged.back().bytes += b.bytes;
-                else merged.push_back(b);
-            }
-            free_list.swap(merged);
-        }
+    p.layout();
+    return UP_OK;
+}
+
+// ---- UniPose-LSTM (model/uniposeLSTM.py:67-138; the drop-in module unipose_amd/uniposeLSTM.py after checkpoint.load_folded) ----
+enum LstmForm { STEP_FIRST, STEP_NEXT, CLIP };
+
+// One program of the video plan.  STEP_FIRST / STEP_NEXT: the module's per-frame path (batch_frames = False) for iter == 0 (LSTM_0)
+// resp. iter > 0 with the caller's NCHW state; CLIP: its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True) — the
+// trunk once on the T * B frame-major images, the recurrence frame by frame on rows of frame-major state tensors, the head once on
+// the T * B hidden states.  Stacked gate convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).
+static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) {
+    const int B = c.batch, T = form == CLIP ? c.frames : 1, n = T * B;
+    const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
+    int h = c.height, w = c.width;
+    Ref x;
+    x.id = p.tensor(n, h, w, 4);
+    {
+        Op op;
+        op.kind = form == CLIP ? CLIP_TO_NHWC : TO_NHWC;
+        op.out = x;
+        op.ext = X;
+        op.n = B; op.a = T; op.c = 3;
+        p.push(op);
     }
-    p.ws_bytes = top;
+    Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true);
+    // _AddCenter: the pooled centre map in the heat-maps' spare pad channel; (K + 1) % 4 == 0: a hand-over tensor of rup4(K + 2)
+    // channels, zeros, the heat-maps copied in
+    Ref z = heat;
+    if (rup4(hc) == hc) {
+        z.id = p.tensor(n, h, w, ldo);
+        p.zero(z);
+        p.copy(heat, hc, z, ldo, 0, (long long)n * h * w, hc);
+    }
+    const int ldz = p.tensors[z.id].c;       // == ldo either way
+    {
+        Op op;
+        op.kind = form == CLIP ? CLIP_POOL : POOL;
+        op.out = z;
+        op.ext = CENTER;
+        op.n = B; op.e = T;
+        op.a = c.height; op.b = c.width; op.c = hc;
+        p.push(op);
+    }
+    // the recurrence: cell / hide of all frames as rows of two frame-major tensors (the head reads the hidden states as one)
+    Ref cells, hides;
+    cells.id = p.tensor(n, h, w, ldo);
+    hides.id = p.tensor(n, h, w, ldo);
+    if (ldo != cg) {                         // pad channels read as zeros (the conv1 of the head reads all ldo)
+        p.zero(cells);
+        p.zero(hides);
+    }
+    const size_t frame = (size_t)B * h * w;
+    for (int t = 0; t < T; ++t) {
+        Ref zt = z, ct = cells, ht = hides;
+        zt.elems += t * frame * ldz;
+        ct.elems += t * frame * ldo;
+        ht.elems += t * frame * ldo;
+        Op op;
+        op.n = B; op.c = cg;
+        op.out = ct; op.res = ht;
+        if (t == 0 && form != STEP_NEXT) {    // LSTM_0 (uniposeLSTM.py:9-24)
+            op.kind = LSTM0;
+            op.in = p.conv("lstm_0", zt, B, h, w, ldz, cg, 3 * cg, 3, 1, 1, 1, 0, true);
+        } else {                              // LSTM (uniposeLSTM.py:27-64): ONE convolution over cat(z, prev_hide)
+            Ref ph, pc;
+            if (form == STEP_NEXT) {          // the caller's NCHW state (unipose._state: ToNHWC, pad channels zero)
+                ph.id = p.tensor(B, h, w, ldo);
+                pc.id = p.tensor(B, h, w, ldo);
+                Op in;
+                in.kind = TO_NHWC;
+                in.n = B; in.c = cg;
+                in.out = ph; in.ext = PREV_HIDE;
+                p.push(in);
+                in.out = pc; in.ext = PREV_CELL;
+                p.push(in);
+            } else {
+                ph = hides;
+                pc = cells;
+                ph.elems += (t - 1) * frame * ldo;
+                pc.elems += (t - 1) * frame * ldo;
+            }
+            Ref zh;
+            zh.id = p.tensor(B, h, w, ldz + ldo);
+            p.copy(zt, ldz, zh, ldz + ldo, 0, (long long)frame, ldz);
+            p.copy(ph, ldo, zh, ldz + ldo, ldz, (long long)frame, ldo);
+            op.kind = LSTM;
+            op.in = p.conv("lstm", zh, B, h, w, ldz + ldo, ldz + ldo, 4 * cg, 3, 1, 1, 1, 0, true);
+            op.aux = pc;
+        }
+        p.push(op);
+    }
+    // the head (uniposeLSTM.py:85-89, 135-138): five convolutions with bias + ReLU
+    Ref y = p.conv("conv1", hides, n, h, w, ldo, cg, 128, 11, 1, 5, 1, 1, true);
+    y = p.conv("conv2", y, n, h, w, 128, 128, 128, 11, 1, 5, 1, 1, true);
+    y = p.conv("conv3", y, n, h, w, 128, 128, 128, 11, 1, 5, 1, 1, true);
+    y = p.conv("conv4", y, n, h, w, 128, 128, 128, 1, 1, 0, 1, 1, true);
+    y = p.conv("conv5", y, n, h, w, 128, 128, hc, 1, 1, 0, 1, 1, true);
+    Op op;
+    op.kind = form == CLIP ? CLIP_TO_NCHW : TO_NCHW;
+    op.in = y;
+    op.ext = HEAT;
+    op.n = B; op.a = T; op.c = hc;
+    p.push(op);
+    Ref cl = cells, hl = hides;                // the state of the last frame
+    cl.elems += (T - 1) * frame * ldo;
+    hl.elems += (T - 1) * frame * ldo;
+    op = Op();
+    op.kind = TO_NCHW;
+    op.n = B; op.c = cg;
+    op.in = cl; op.ext = CELL;
+    p.push(op);
+    op.in = hl; op.ext = HIDE;
+    p.push(op);
+    p.layout();
+}
+
+// caller-owned tensors of one call
+struct Io {
+    const float* x = nullptr;
+    const float* center = nullptr;
+    const float* prev_hide = nullptr;
+    const float* prev_cell = nullptr;
+    float* heat = nullptr;
+    float* cell = nullptr;
+    float* hide = nullptr;
+    const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
+    float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
+};
+
+static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, const char* what) {
+    auto ptr = [&](const Ref& r) -> float* {
+        return r.id < 0 ? nullptr : reinterpret_cast<float*>(ws + p.tensors[r.id].off) + r.elems;
+    };
+    auto T_ = [&](const Ref& r) -> const Tensor& { return p.tensors[r.id]; };
+    for (const Op& op : p.ops) {
+        int e = UP_OK;
+        switch (op.kind) {
+        case TO_NHWC:
+            e = up_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            break;
+        case CONV: {
+            const Conv& cv = p.convs[op.conv];
+            up_conv_epilogue ep;
+            memset(&ep, 0, sizeof(ep));
+            ep.bias = cv.bias;
+            ep.residual = ptr(op.res);
+            ep.ldr = op.res.id >= 0 ? T_(op.res).c : 0;
+            ep.relu = cv.relu;
+            e = up_conv2d_fwd(&cv.d, ptr(op.in), cv.w_fwd, ptr(op.out), &ep, stream);
+            break;
+        }
+        case MAXPOOL:
+            e = up_maxpool3s2_fwd(ptr(op.in), op.c, ptr(op.out), op.c, reinterpret_cast<uint8_t*>(ptr(op.res)), op.n, op.a, op.b, op.c,
+                                  (op.a - 1) / 2 + 1, (op.b - 1) / 2 + 1, stream);
+            break;
+        case BILINEAR:
+            e = up_bilinear_fwd(ptr(op.in), op.c, ptr(op.out), op.c, op.n, op.a, op.b, op.c, op.e >> 16, op.e & 65535, stream);
+            break;
+        case GAP:
+            e = up_gap_fwd(ptr(op.in), op.c, ptr(op.out), op.n, op.a, op.c, stream);
+            break;
+        case COPY:
+            e = up_copy2d(ptr(op.in), op.a, ptr(op.out), op.b, op.e, op.c, stream);
+            break;
+        case ZERO:
+            if (hipMemsetAsync(ptr(op.out), 0, T_(op.out).bytes, as_stream(stream)) != hipSuccess) e = check_launch(what);
+            break;
+        case TO_NCHW:
+            if (io.out(op.ext))
+                e = up_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.out(op.ext), op.n, op.c, T_(op.in).h, T_(op.in).w, stream);
+            break;
+        case POOL:
+            e = up_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.a, op.b, T_(op.out).h, T_(op.out).w, stream);
+            break;
+        case CLIP_POOL:
+            e = up_clip_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.e, op.a, op.b, T_(op.out).h, T_(op.out).w,
+                                       stream);
+            break;
+        case LSTM0:
+            e = up_lstm0_fwd(ptr(op.in), T_(op.in).c, ptr(op.out), ptr(op.res), T_(op.out).c, (int64_t)op.n * T_(op.in).h * T_(op.in).w,
+                             op.c, stream);
+            break;
+        case LSTM:
+            e = up_lstm_fwd(ptr(op.in), T_(op.in).c, ptr(op.aux), T_(op.aux).c, ptr(op.out), ptr(op.res), T_(op.out).c,
+                            (int64_t)op.n * T_(op.in).h * T_(op.in).w, op.c, stream);
+            break;
+        case CLIP_TO_NHWC:
+            e = up_clip_nchw_to_nhwc(io.x, ptr(op.out), op.n, op.a, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            break;
+        case CLIP_TO_NCHW:
+            e = up_clip_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.heat, op.n, op.a, op.c, T_(op.in).h, T_(op.in).w, stream);
+            break;
+        }
+        if (e) return e;
+    }
     return UP_OK;
 }
 
@@ -332,6 +562,7 @@ using namespace up;
 using up::plan::Plan;
 
 struct up_unipose_plan {
+    up_unipose_config cfg;
     Plan p;
 };
 
@@ -343,8 +574,8 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
                "unipose_plan_create: output stride %d (the reference builds 16 and 8, resnet.py:49-58)", cfg->output_stride);
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
-    pl->p.cfg = *cfg;
-    if (int e = up::plan::build(pl->p)) {
+    pl->cfg = *cfg;
+    if (int e = up::plan::build(pl->p, pl->cfg)) {
         delete pl;
         return e;
     }
@@ -418,50 +649,236 @@ extern "C" int up_unipose_forward(up_unipose_plan* pl, const float* x_nchw, floa
         UP_REQUIRE(cv.set, UP_ERR_INVALID, "unipose_forward: weights of %s were never set (up_unipose_plan_set_conv)", cv.name.c_str());
     UP_REQUIRE(ws_bytes >= pl->p.ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_INVALID,
                "unipose_forward: workspace of %zu bytes (256-byte aligned) needed, got %zu", pl->p.ws_bytes, ws_bytes);
-    Plan& p = pl->p;
-    const up_unipose_config& c = p.cfg;
-    unsigned char* const ws = static_cast<unsigned char*>(workspace);
-    auto ptr = [&](const plan::Ref& r) -> float* {
-        return r.id < 0 ? nullptr : reinterpret_cast<float*>(ws + p.tensors[r.id].off) + r.elems;
-    };
-    for (const plan::Op& op : p.ops) {
-        int e = UP_OK;
-        switch (op.kind) {
-        case plan::TO_NHWC:
-            e = up_nchw_to_nhwc(x_nchw, ptr(op.out), c.batch, 3, c.height, c.width, 4, stream);
-            break;
-        case plan::CONV: {
-            const plan::Conv& cv = p.convs[op.conv];
-            up_conv_epilogue ep;
-            memset(&ep, 0, sizeof(ep));
-            ep.bias = cv.bias;
-            ep.residual = ptr(op.res);
-            ep.ldr = op.res.id >= 0 ? p.tensors[op.res.id].c : 0;
-            ep.relu = cv.relu;
-            e = up_conv2d_fwd(&cv.d, ptr(op.in), cv.w_fwd, ptr(op.out), &ep, stream);
-            break;
-        }
-        case plan::MAXPOOL:
-            e = up_maxpool3s2_fwd(ptr(op.in), op.c, ptr(op.out), op.c, reinterpret_cast<uint8_t*>(ptr(op.res)), c.batch, op.a, op.b, op.c,
-                                  (op.a - 1) / 2 + 1, (op.b - 1) / 2 + 1, stream);
-            break;
-        case plan::BILINEAR:
-            e = up_bilinear_fwd(ptr(op.in), op.c, ptr(op.out), op.c, c.batch, op.a, op.b, op.c, op.e >> 16, op.e & 65535, stream);
-            break;
-        case plan::GAP:
-            e = up_gap_fwd(ptr(op.in), op.c, ptr(op.out), c.batch, op.a, op.c, stream);
-            break;
-        case plan::COPY:
-            e = up_copy2d(ptr(op.in), op.a, ptr(op.out), op.b, op.e, op.c, stream);
-            break;
-        case plan::ZERO:
-            if (hipMemsetAsync(ptr(op.out), 0, p.tensors[op.out.id].bytes, as_stream(stream)) != hipSuccess) e = check_launch("unipose_forward memset");
-            break;
-        case plan::TO_NCHW:
-            e = up_nhwc_to_nchw(ptr(op.in), op.e, heat_nchw, c.batch, op.c, op.a, op.b, stream);
-            break;
-        }
-        if (e) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.heat = heat_nchw;
+    return plan::run(pl->p, io, static_cast<unsigned char*>(workspace), stream, "unipose_forward");
+}
+
+// ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------
+// Three programs share one weight store: the per-frame step for the first frame (LSTM_0) and for a later one (LSTM over the
+// caller's state), and the whole clip.  Weights are stored once per distinct parameter; the ConvLSTM gate convolutions are set
+// part by part under their state_dict names and stacked by the plan (modules.LSTM_0.forward / modules.LSTM.stacked): along the
+// output channels, the x / h parts' input channels padded to rup4, each gate bias the fp32 sum bx + bh.
+namespace up {
+namespace plan {
+
+struct Store {                 // one packed forward weight image (+ bias)
+    std::string name;          // a state_dict prefix, or "lstm_0" / "lstm" for the stacked gate convolutions
+    up_conv_desc d;            // descriptor of its first use (the packed image depends on K, C, Cp, R, S only)
+    bool has_bias = false;
+    float* w_fwd = nullptr;
+    float* bias = nullptr;
+    int parts = 0;             // stacked: 3 (g, i, o) or 8 (gx, ix, ox, fx, gh, ih, oh, fh), else 0
+    float* stage_w = nullptr;  // stacked: the OIHW image the parts are copied into (pad channels zero)
+    float* stage_b = nullptr;  // stacked: [parts][cg] the parts' biases
+    bool staged = false;       // stage_w zeroed (on the stream of the first set_conv)
+};
+struct Entry {                 // one listed convolution
+    std::string name;
+    int32_t oihw[4];
+    bool has_bias;
+    int store;
+    int part = -1;             // >= 0: slot of a stacked gate weight
+    bool set = false;
+};
+
+}  // namespace plan
+}  // namespace up
+
+struct up_unipose_lstm_plan {
+    up_unipose_lstm_config cfg;
+    Plan prog[3];              // STEP_FIRST, STEP_NEXT, CLIP
+    std::vector<plan::Store> stores;
+    std::vector<plan::Entry> entries;
+    size_t ws_bytes = 0;
+};
+
+extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** out) {
+    UP_REQUIRE(cfg && out, UP_ERR_INVALID, "unipose_lstm_plan_create: null argument");
+    UP_REQUIRE(cfg->batch > 0 && cfg->frames > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->num_classes > 0, UP_ERR_INVALID,
+               "unipose_lstm_plan_create: batch %d, %d frames, input %dx%d, %d classes", cfg->batch, cfg->frames, cfg->height,
+               cfg->width, cfg->num_classes);
+    UP_REQUIRE(cfg->output_stride == 16 || cfg->output_stride == 8, UP_ERR_UNSUPPORTED,
+               "unipose_lstm_plan_create: output stride %d (the reference builds 16 and 8, resnet.py:49-58)", cfg->output_stride);
+    // the trunk's heat-maps are ceil(H / 8) high, the pooled centre map (H - 7) / 8 + 1 (AvgPool2d(9, 8, 1)): the module's
+    // cat fails where they differ (H % 8 not in {0, 7}), the plan would write out of bounds
+    UP_REQUIRE((cfg->height - 1) / 8 + 1 == (cfg->height - 7) / 8 + 1 && (cfg->width - 1) / 8 + 1 == (cfg->width - 7) / 8 + 1,
+               UP_ERR_UNSUPPORTED,
+               "unipose_lstm_plan_create: input %dx%d gives %dx%d heat-maps but %dx%d pooled centre maps (H, W %% 8 must be 0 or 7)",
+               cfg->height, cfg->width, (cfg->height - 1) / 8 + 1, (cfg->width - 1) / 8 + 1, (cfg->height - 7) / 8 + 1,
+               (cfg->width - 7) / 8 + 1);
+    up_unipose_lstm_plan* pl = new (std::nothrow) up_unipose_lstm_plan();
+    UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_lstm_plan_create: out of host memory");
+    pl->cfg = *cfg;
+    for (int f = 0; f < 3; ++f) {
+        plan::build_lstm(pl->prog[f], pl->cfg, static_cast<plan::LstmForm>(f));
+        pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
     }
+    // the weight store: every distinct name of the three programs
+    auto store_of = [&](const std::string& name) {
+        for (size_t s = 0; s < pl->stores.size(); ++s)
+            if (pl->stores[s].name == name) return (int)s;
+        return -1;
+    };
+    for (Plan& p : pl->prog)
+        for (const plan::Conv& cv : p.convs) {
+            if (store_of(cv.name) >= 0) continue;
+            plan::Store st;
+            st.name = cv.name;
+            st.d = cv.d;
+            st.has_bias = cv.has_bias;
+            st.parts = cv.name == "lstm_0" ? 3 : cv.name == "lstm" ? 8 : 0;
+            pl->stores.push_back(st);
+        }
+    const int cg = cfg->num_classes + 2;
+    bool ok = true;
+    for (plan::Store& st : pl->stores) {
+        st.w_fwd = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * st.d.R * st.d.S * st.d.Cp * sizeof(float)));
+        if (st.has_bias) st.bias = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * sizeof(float)));
+        ok = ok && st.w_fwd && (!st.has_bias || st.bias);
+        if (st.parts) {
+            st.stage_w = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * st.d.C * st.d.R * st.d.S * sizeof(float)));
+            st.stage_b = static_cast<float*>(plan::dev_alloc((size_t)st.parts * cg * sizeof(float)));
+            ok = ok && st.stage_w && st.stage_b;
+        }
+    }
+    for (Plan& p : pl->prog)
+        for (plan::Conv& cv : p.convs) {
+            const plan::Store& st = pl->stores[store_of(cv.name)];
+            cv.w_fwd = st.w_fwd;
+            cv.bias = st.bias;
+        }
+    // the listed convolutions: the trunk in program order (wasp.conv2 twice, like the image plan), the gate parts, the head
+    static const char* const gates0[3] = {"g", "i", "o"};
+    static const char* const gates[8] = {"gx", "ix", "ox", "fx", "gh", "ih", "oh", "fh"};
+    auto entry = [&](const std::string& name, int store, int part, int k, int c, int r, bool bias) {
+        plan::Entry e;
+        e.name = name;
+        e.oihw[0] = k; e.oihw[1] = c; e.oihw[2] = r; e.oihw[3] = r;
+        e.has_bias = bias;
+        e.store = store;
+        e.part = part;
+        pl->entries.push_back(e);
+    };
+    for (const plan::Conv& cv : pl->prog[plan::STEP_FIRST].convs) {
+        if (cv.name == "lstm_0") {
+            for (int i = 0; i < 3; ++i)
+                entry(std::string("lstm_0.conv_") + gates0[i] + "_lstm", store_of("lstm_0"), i, cg, cg, 3, true);
+            for (int i = 0; i < 8; ++i)
+                entry(std::string("lstm.conv_") + gates[i] + "_lstm", store_of("lstm"), i, cg, cg, 3, true);
+            continue;
+        }
+        entry(cv.name, store_of(cv.name), -1, cv.d.K, cv.d.C, cv.d.R, cv.has_bias);
+    }
+    if (!ok) {
+        up_unipose_lstm_plan_destroy(pl);
+        UP_REQUIRE(false, UP_ERR_INVALID, "unipose_lstm_plan_create: out of device memory");
+    }
+    *out = pl;
     return UP_OK;
+}
+
+extern "C" void up_unipose_lstm_plan_destroy(up_unipose_lstm_plan* pl) {
+    if (!pl) return;
+    for (plan::Store& st : pl->stores) {
+        plan::dev_free(st.w_fwd);
+        plan::dev_free(st.bias);
+        plan::dev_free(st.stage_w);
+        plan::dev_free(st.stage_b);
+    }
+    delete pl;
+}
+
+extern "C" int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* pl) { return pl ? (int)pl->entries.size() : UP_ERR_INVALID; }
+
+extern "C" const char* up_unipose_lstm_plan_conv_name(const up_unipose_lstm_plan* pl, int i) {
+    return (pl && i >= 0 && i < (int)pl->entries.size()) ? pl->entries[i].name.c_str() : "";
+}
+
+extern "C" int up_unipose_lstm_plan_conv_shape(const up_unipose_lstm_plan* pl, int i, int32_t* oihw, int32_t* has_bias) {
+    UP_REQUIRE(pl && oihw && i >= 0 && i < (int)pl->entries.size(), UP_ERR_INVALID, "unipose_lstm_plan_conv_shape: bad argument");
+    const plan::Entry& e = pl->entries[i];
+    memcpy(oihw, e.oihw, sizeof(e.oihw));
+    if (has_bias) *has_bias = e.has_bias ? 1 : 0;
+    return UP_OK;
+}
+
+extern "C" int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* pl, int i, const float* w_oihw, const float* bias, void* stream) {
+    UP_REQUIRE(pl && w_oihw && i >= 0 && i < (int)pl->entries.size(), UP_ERR_INVALID, "unipose_lstm_plan_set_conv: bad argument");
+    plan::Entry& en = pl->entries[i];
+    plan::Store& st = pl->stores[en.store];
+    UP_REQUIRE((bias != nullptr) == en.has_bias, UP_ERR_INVALID, "unipose_lstm_plan_set_conv: %s %s a bias (folded network)",
+               en.name.c_str(), en.has_bias ? "needs" : "has no");
+    if (en.part < 0) {
+        if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) return e;
+        if (bias)
+            if (int e = up_copy2d(bias, st.d.K, st.bias, st.d.K, 1, st.d.K, stream)) return e;
+        for (plan::Entry& other : pl->entries)
+            if (other.name == en.name) other.set = true;
+        return UP_OK;
+    }
+    // a gate part: rows [gate * cg, (gate + 1) * cg) of the stacked OIHW image, input channels from xoff on
+    const int cg = pl->cfg.num_classes + 2, taps = st.d.R * st.d.S;
+    const int gate = en.part % 4, xoff = st.parts == 8 && en.part >= 4 ? st.d.C / 2 : 0;
+    if (!st.staged) {
+        if (hipMemsetAsync(st.stage_w, 0, (size_t)st.d.K * st.d.C * taps * sizeof(float), as_stream(stream)) != hipSuccess)
+            return check_launch("unipose_lstm_plan_set_conv memset");
+        st.staged = true;
+    }
+    if (int e = up_copy2d(w_oihw, cg * taps, st.stage_w + ((size_t)gate * cg * st.d.C + xoff) * taps, st.d.C * taps, cg, cg * taps,
+                          stream))
+        return e;
+    if (int e = up_copy2d(bias, cg, st.stage_b + (size_t)en.part * cg, cg, 1, cg, stream)) return e;
+    en.set = true;
+    for (const plan::Entry& other : pl->entries)
+        if (other.store == en.store && !other.set) return UP_OK;
+    // every part is set: the stacked bias (LSTM_0: g | i | o; LSTM: bx + bh per gate) and the packed image
+    int e = st.parts == 3 ? up_copy2d(st.stage_b, 3 * cg, st.bias, 3 * cg, 1, 3 * cg, stream)
+                          : up_add2d(st.stage_b, cg, st.stage_b + 4 * cg, cg, st.bias, cg, 4, cg, stream);
+    if (e) return e;
+    return up_pack_weights(&st.d, st.stage_w, st.w_fwd, nullptr, stream);
+}
+
+extern "C" size_t up_unipose_lstm_plan_workspace(const up_unipose_lstm_plan* pl) { return pl ? pl->ws_bytes : 0; }
+
+static int lstm_ready(const up_unipose_lstm_plan* pl, const void* workspace, size_t ws_bytes, const char* what) {
+    for (const plan::Entry& e : pl->entries)
+        UP_REQUIRE(e.set, UP_ERR_INVALID, "%s: weights of %s were never set (up_unipose_lstm_plan_set_conv)", what, e.name.c_str());
+    UP_REQUIRE(ws_bytes >= pl->ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_WORKSPACE,
+               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, pl->ws_bytes, ws_bytes);
+    return UP_OK;
+}
+
+extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nchw, const float* center_nchw, const float* prev_hide,
+                                    const float* prev_cell, float* heat_nchw, float* cell_nchw, float* hide_nchw, void* workspace,
+                                    size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && center_nchw && heat_nchw && cell_nchw && hide_nchw && workspace, UP_ERR_INVALID,
+               "unipose_lstm_step: null argument");
+    UP_REQUIRE((prev_hide == nullptr) == (prev_cell == nullptr), UP_ERR_INVALID,
+               "unipose_lstm_step: prev_hide and prev_cell are both given (a later frame) or both NULL (the first frame)");
+    if (int e = lstm_ready(pl, workspace, ws_bytes, "unipose_lstm_step")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.center = center_nchw;
+    io.prev_hide = prev_hide;
+    io.prev_cell = prev_cell;
+    io.heat = heat_nchw;
+    io.cell = cell_nchw;
+    io.hide = hide_nchw;
+    return plan::run(pl->prog[prev_hide ? plan::STEP_NEXT : plan::STEP_FIRST], io, static_cast<unsigned char*>(workspace), stream,
+                     "unipose_lstm_step");
+}
+
+extern "C" int up_unipose_lstm_clip(up_unipose_lstm_plan* pl, const float* x, const float* center, float* heat, float* cell_last,
+                                    float* hide_last, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x && center && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip: null argument");
+    if (int e = lstm_ready(pl, workspace, ws_bytes, "unipose_lstm_clip")) return e;
+    plan::Io io;
+    io.x = x;
+    io.center = center;
+    io.heat = heat;
+    io.cell = cell_last;
+    io.hide = hide_last;
+    return plan::run(pl->prog[plan::CLIP], io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip");
 }

@@ -16,6 +16,9 @@ static inline int grid_cap(int64_t work_items, int cap = 8192) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (total); i += (int64_t)gridDim.x * 256)
 
 // ---- layout ------------------------------------------------------------------------------
+// channel c of the NCHW pixel at `src` (planes HW apart); the pad channels C <= c < ld of an NHWC row read as zeros
+__device__ __forceinline__ float nchw_at(const float* src, int C, int HW, int c) { return c < C ? src[(int64_t)c * HW] : 0.f; }
+
 template <typename TO>
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* x, TO* y, int C, int HW, int ld,
                                                            int64_t npix) {
@@ -24,7 +27,7 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* x, TO* y
         int hw = (int)(i - n * HW);
         const float* src = x + n * C * HW + hw;
         TO* dst = y + i * ld;
-        for (int c = 0; c < ld; ++c) st1(dst + c, c < C ? src[(int64_t)c * HW] : 0.f);
+        for (int c = 0; c < ld; ++c) st1(dst + c, nchw_at(src, C, HW, c));
     }
 }
 template <typename TI>
@@ -36,6 +39,43 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const TI* x, int ld, 
         const TI* src = x + i * ld;
         float* dst = y + n * C * HW + hw;
         for (int c = 0; c < C; ++c) dst[(int64_t)c * HW] = ld1(src + c);
+    }
+}
+
+// Clip layout (the video plan, plan.hip): a clip is batch-major, (B, T, ...), the trunk and the head run frame-major, on T * B
+// images with image f = t * B + b.  One thread per frame-major pixel; the NHWC side moves 16-byte channel quads (a wave writes
+// resp. reads 1 KiB of consecutive pixels per instruction), the NCHW side one plane per channel, consecutive pixels on
+// consecutive lanes.  ld % 4 == 0 and 16-byte aligned NHWC pointers (checked by the host wrappers).
+__device__ __forceinline__ int64_t clip_image(int64_t f, int B, int T) {      // frame-major image f -> batch-major image b * T + t
+    const int64_t t = f / B;
+    return (f - t * B) * T + t;
+}
+__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_kernel(const float* x, float* y, int B, int T, int C, int HW, int ld,
+                                                                int64_t npix) {
+    UP_GRID_STRIDE(i, npix) {
+        const int64_t f = i / HW;
+        const int hw = (int)(i - f * HW);
+        const float* src = x + clip_image(f, B, T) * C * HW + hw;
+        float* dst = y + i * ld;
+        for (int c = 0; c < ld; c += 4)
+            *reinterpret_cast<float4*>(dst + c) =
+                make_float4(nchw_at(src, C, HW, c), nchw_at(src, C, HW, c + 1), nchw_at(src, C, HW, c + 2), nchw_at(src, C, HW, c + 3));
+    }
+}
+__global__ void __launch_bounds__(256) clip_nhwc_to_nchw_kernel(const float* x, int ld, float* y, int B, int T, int C, int HW,
+                                                                int64_t npix) {
+    UP_GRID_STRIDE(i, npix) {
+        const int64_t f = i / HW;
+        const int hw = (int)(i - f * HW);
+        const float* src = x + i * ld;
+        float* dst = y + clip_image(f, B, T) * C * HW + hw;
+        for (int c = 0; c < C; c += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(src + c);
+            dst[(int64_t)c * HW] = v.x;
+            if (c + 1 < C) dst[(int64_t)(c + 1) * HW] = v.y;
+            if (c + 2 < C) dst[(int64_t)(c + 2) * HW] = v.z;
+            if (c + 3 < C) dst[(int64_t)(c + 3) * HW] = v.w;
+        }
     }
 }
 
@@ -292,6 +332,20 @@ __global__ void __launch_bounds__(256) gap_bwd_kernel(const T* dy, T* dx, int ld
 }
 
 // ---- AvgPool2d(9, 8, 1), count_include_pad -----------------------------------------------------
+// output pixel (p, q) of the H x W plane `x`: the arithmetic of both launches below (a clip's centre maps pool to the same bits)
+__device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int p, int q) {
+    int hs = p * 8 - 1, ws = q * 8 - 1;
+    int he = min(hs + 9, H + 1), we = min(ws + 9, W + 1);
+    float div = (float)((he - hs) * (we - ws));
+    hs = max(hs, 0);
+    ws = max(ws, 0);
+    he = min(he, H);
+    we = min(we, W);
+    float s = 0.f;
+    for (int h = hs; h < he; ++h)
+        for (int w = ws; w < we; ++w) s += x[h * W + w];
+    return s / div;
+}
 __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int H, int W,
                                                          int P, int Q, int64_t total) {
     UP_GRID_STRIDE(i, total) {
@@ -299,17 +353,18 @@ __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* 
         int64_t t = i / Q;
         int p = (int)(t % P);
         int64_t n = t / P;
-        int hs = p * 8 - 1, ws = q * 8 - 1;
-        int he = min(hs + 9, H + 1), we = min(ws + 9, W + 1);
-        float div = (float)((he - hs) * (we - ws));
-        hs = max(hs, 0);
-        ws = max(ws, 0);
-        he = min(he, H);
-        we = min(we, W);
-        float s = 0.f;
-        for (int h = hs; h < he; ++h)
-            for (int w = ws; w < we; ++w) s += x[(n * H + h) * W + w];
-        y[i * ldy + coff] = s / div;
+        y[i * ldy + coff] = avgpool9s8_at(x + n * H * W, H, W, p, q);
+    }
+}
+// ... of a clip's (B, T, 1, H, W) centre maps into channel coff of the frame-major (T * B, P, Q, ldy) hand-over tensor
+__global__ void __launch_bounds__(256) clip_avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int B, int T, int H,
+                                                              int W, int P, int Q, int64_t total) {
+    UP_GRID_STRIDE(i, total) {
+        int q = (int)(i % Q);
+        int64_t t = i / Q;
+        int p = (int)(t % P);
+        int64_t f = t / P;
+        y[i * ldy + coff] = avgpool9s8_at(x + clip_image(f, B, T) * H * W, H, W, p, q);
     }
 }
 
@@ -657,6 +712,21 @@ extern "C" int up_nhwc_to_nchw(const float* x, int ldx, float* y, int N, int C, 
     return up_nhwc_to_nchw_t(x, ldx, y, N, C, H, W, UP_DT_F32, stream);
 }
 
+extern "C" int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldy >= C && ldy % 4 == 0 && (uintptr_t)y % 16 == 0,
+               UP_ERR_INVALID, "clip_nchw_to_nhwc: bad argument");
+    int64_t npix = (int64_t)T * B * H * W;
+    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel, npix, as_stream(stream), x, y, B, T, C, H * W, ldy, npix);
+    return check_launch("clip_nchw_to_nhwc");
+}
+extern "C" int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && (uintptr_t)x % 16 == 0,
+               UP_ERR_INVALID, "clip_nhwc_to_nchw: bad argument");
+    int64_t npix = (int64_t)T * B * H * W;
+    UP_LAUNCH_1D(clip_nhwc_to_nchw_kernel, npix, as_stream(stream), x, ldx, y, B, T, C, H * W, npix);
+    return check_launch("clip_nhwc_to_nchw");
+}
+
 extern "C" int up_copy2d(const float* s, int lds, float* d, int ldd, int64_t rows, int C, void* stream) {
     UP_REQUIRE(s && d && rows > 0 && C > 0 && lds >= C && ldd >= C, UP_ERR_INVALID, "copy2d: bad argument");
     UP_REQUIRE(rows * C < (1ll << 31), UP_ERR_UNSUPPORTED, "copy2d: tensor too large");
@@ -826,6 +896,15 @@ extern "C" int up_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, in
     int64_t total = (int64_t)N * P * Q;
     UP_LAUNCH_1D(avgpool9s8_kernel, total, as_stream(stream), x, y, ldy, coff, H, W, P, Q, total);
     return check_launch("avgpool9s8");
+}
+
+extern "C" int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                                      void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && H > 0 && W > 0 && coff >= 0 && coff < ldy, UP_ERR_INVALID, "clip_avgpool: bad argument");
+    UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1, UP_ERR_INVALID, "clip_avgpool: P,Q mismatch");
+    int64_t total = (int64_t)T * B * P * Q;
+    UP_LAUNCH_1D(clip_avgpool9s8_kernel, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
+    return check_launch("clip_avgpool9s8");
 }
 
 extern "C" int up_lstm0_fwd(const float* gates, int ldg, float* cell, float* hide, int ldo, int64_t rows, int Cg,

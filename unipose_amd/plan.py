@@ -29,6 +29,39 @@ class _Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "output_stride", "out_channels")]
 
 
+def _set_convs(plan, prefix, folded):
+    """every convolution the plan lists, from the folded state dict (`prefix`: up_unipose_plan / up_unipose_lstm_plan)"""
+    L = _C.lib()
+    who = type(plan).__name__
+    keep = []
+    shape = (C.c_int32 * 4)()
+    hb = C.c_int32()
+    for i in range(getattr(L, prefix + "_num_convs")(plan._plan)):
+        name = getattr(L, prefix + "_conv_name")(plan._plan, i).decode()
+        _C.check(getattr(L, prefix + "_conv_shape")(plan._plan, i, shape, C.byref(hb)), prefix[3:] + "_conv_shape")
+        w = folded[name + ".weight"].to(plan.device, torch.float32).contiguous()
+        if tuple(w.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name}.weight is {tuple(w.shape)}, the plan expects {tuple(shape)}")
+        b = folded.get(name + ".bias")
+        if bool(hb.value) != (b is not None):
+            raise ValueError(f"{who}: {name} {'needs' if hb.value else 'must not have'} a bias after folding")
+        if b is not None:
+            b = b.to(plan.device, torch.float32).contiguous()
+        _C.check(getattr(L, prefix + "_set_conv")(plan._plan, i, w.data_ptr(), None if b is None else b.data_ptr(), plan._stream()),
+                 prefix[3:] + "_set_conv")
+        keep += [w, b]
+    if plan.device.type == "cuda":
+        torch.cuda.current_stream(plan.device).synchronize()       # the staging tensors in `keep` may go now
+    del keep
+
+
+def _check_out(who, name, t, shape, dev):
+    if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{who}: `{name}` is {tuple(t.shape)} {t.dtype} on {t.device} (contiguous: {t.is_contiguous()}), "
+                         f"the plan writes a contiguous float32 {shape} on {dev}")
+    return t
+
+
 class UniPosePlan:
     def __init__(self, model, batch: int, height: int, width: int):
         if model.training:
@@ -61,28 +94,7 @@ class UniPosePlan:
 
     def refresh(self, model):
         """(re)load the weights: BatchNorm folded in float64 and rounded once, like checkpoint.fold_batchnorm / load_folded"""
-        L = _C.lib()
-        folded = fold_batchnorm(model)
-        keep = []
-        shape = (C.c_int32 * 4)()
-        hb = C.c_int32()
-        for i in range(L.up_unipose_plan_num_convs(self._plan)):
-            name = L.up_unipose_plan_conv_name(self._plan, i).decode()
-            _C.check(L.up_unipose_plan_conv_shape(self._plan, i, shape, C.byref(hb)), "unipose_plan_conv_shape")
-            w = folded[name + ".weight"].to(self.device, torch.float32).contiguous()
-            if tuple(w.shape) != tuple(shape):
-                raise ValueError(f"UniPosePlan: {name}.weight is {tuple(w.shape)}, the plan expects {tuple(shape)}")
-            b = folded.get(name + ".bias")
-            if bool(hb.value) != (b is not None):
-                raise ValueError(f"UniPosePlan: {name} {'needs' if hb.value else 'must not have'} a bias after folding")
-            if b is not None:
-                b = b.to(self.device, torch.float32).contiguous()
-            _C.check(L.up_unipose_plan_set_conv(self._plan, i, w.data_ptr(), None if b is None else b.data_ptr(), self._stream()),
-                     "unipose_plan_set_conv")
-            keep += [w, b]
-        if self.device.type == "cuda":
-            torch.cuda.current_stream(self.device).synchronize()       # the staging tensors in `keep` may go now
-        del keep
+        _set_convs(self, "up_unipose_plan", fold_batchnorm(model))
 
     def __call__(self, x: torch.Tensor, out: torch.Tensor = None):
         if tuple(x.shape) != (self.batch, 3, self.height, self.width) or x.dtype != torch.float32 or x.device != self.device:
@@ -106,6 +118,126 @@ class UniPosePlan:
     def close(self):
         if self._plan:
             _C.lib().up_unipose_plan_destroy(self._plan)
+            self._plan = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class _LstmConfig(C.Structure):
+    """up_unipose_lstm_config"""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "frames", "height", "width", "output_stride", "num_classes")]
+
+
+class UniPoseLSTMPlan:
+    """The video model's inference forward through the C ABI (``up_unipose_lstm_step`` / ``up_unipose_lstm_clip``, ABI 10 additions).
+
+    Built from an eval-mode ``unipose_lstm`` (BatchNorm folded like ``checkpoint.fold_batchnorm``).  Two forms, equal bits to the
+    folded module (``checkpoint.load_folded``):
+
+        plan = UniPoseLSTMPlan(model, batch=1, height=368, width=368, frames=5)
+        heat, cell, hide = plan.step(x[:, 0], cm[:, 0])                    # the first frame (LSTM_0) ...
+        heat, cell, hide = plan.step(x[:, 1], cm[:, 1], (hide, cell))      # ... a later one: the module's per-frame path
+        heats, cell, hide = plan.clip(x, cm)     # (B, T, K+1, h, w) + the last frame's state: the module's whole-clip unroll
+
+    The state is the caller's, NCHW (B, K+2, h, w) as the reference's signature has it; the (K+2, h, w) zeros of the reference's
+    first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
+    module ignores them at iter == 0).  Weights are captured at construction: ``refresh(model)`` after changing them.  Inference only.
+    """
+
+    def __init__(self, model, batch: int, height: int, width: int, frames: int = 1):
+        if model.training:
+            raise ValueError("UniPoseLSTMPlan captures the inference forward: call model.eval() first")
+        if getattr(model, "stride", 8) != 8:
+            raise NotImplementedError("UniPoseLSTMPlan: stride != 8 is not planned")
+        if batch < 1 or frames < 1 or height < 8 or width < 8:
+            raise ValueError(f"UniPoseLSTMPlan: batch {batch}, {frames} frames, {height} x {width} input")
+        w0 = model.backbone.conv1.weight
+        if not w0.is_cuda and not _C._ALLOW_HOST_POINTERS:
+            raise _C.UniPoseHipError("UniPoseLSTMPlan needs a CUDA(HIP) model; there is no CPU fallback")
+        self.device = w0.device
+        self.num_classes = K = model.num_classes
+        os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
+        self.cfg = _LstmConfig(batch, frames, height, width, os_, K)
+        self._plan = C.c_void_p()
+        L = _C.lib()
+        _C.check(L.up_unipose_lstm_plan_create(C.byref(self.cfg), C.byref(self._plan)), "unipose_lstm_plan_create")
+        self.batch, self.frames, self.height, self.width = batch, frames, height, width
+        self.out_height, self.out_width = (height - 1) // 8 + 1, (width - 1) // 8 + 1
+        self.workspace = torch.empty(max(L.up_unipose_lstm_plan_workspace(self._plan), 256) + 256, dtype=torch.uint8,
+                                     device=self.device)
+        self.refresh(model)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+
+    def refresh(self, model):
+        """(re)load the weights: BatchNorm folded in float64 and rounded once; the gate weights are stacked by the plan"""
+        _set_convs(self, "up_unipose_lstm_plan", fold_batchnorm(model))
+
+    def _input(self, t, shape, what):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device:
+            raise ValueError(f"UniPoseLSTMPlan: {what} {tuple(t.shape)} {t.dtype} on {t.device}, planned for {shape} float32 on "
+                             f"{self.device}")
+        return t.contiguous()
+
+    def _state(self, t, what):
+        c = (self.num_classes + 2, self.out_height, self.out_width)
+        if t.dim() == 3 and tuple(t.shape) == c:
+            t = t.unsqueeze(0).expand(self.batch, -1, -1, -1)
+        return self._input(t, (self.batch,) + c, what)
+
+    def _outs(self, out, shapes):
+        names = ("heat", "cell", "hide")
+        if out is None:
+            return tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        if len(out) != 3:
+            raise ValueError("UniPoseLSTMPlan: `out` is a (heat, cell, hide) triple")
+        return tuple(_check_out("UniPoseLSTMPlan", n, t, s, self.device) for n, t, s in zip(names, out, shapes))
+
+    def _ws(self):
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def step(self, frame: torch.Tensor, centermap: torch.Tensor, prev=None, first: bool = None, out=None):
+        """One frame: frame (B, 3, H, W), centermap (B, 1, H, W), prev = None or (hide, cell) -> heat (B, K+1, h, w), cell, hide
+        (B, K+2, h, w).  first (default: prev is None) selects LSTM_0, which reads no state."""
+        B, H, W, h, w, K = self.batch, self.height, self.width, self.out_height, self.out_width, self.num_classes
+        x = self._input(frame, (B, 3, H, W), "frame")
+        cm = self._input(centermap, (B, 1, H, W), "centre map")
+        if first is None:
+            first = prev is None
+        if not first and prev is None:
+            raise ValueError("UniPoseLSTMPlan.step: a later frame needs the previous (hide, cell)")
+        ph = pc = None
+        if not first:
+            ph, pc = self._state(prev[0], "previous hide"), self._state(prev[1], "previous cell")
+        heat, cell, hide = self._outs(out, [(B, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
+        ws, nbytes = self._ws()
+        _C.check(_C.lib().up_unipose_lstm_step(self._plan, x.data_ptr(), cm.data_ptr(), None if first else ph.data_ptr(),
+                                               None if first else pc.data_ptr(), heat.data_ptr(), cell.data_ptr(), hide.data_ptr(),
+                                               ws, nbytes, self._stream()), "unipose_lstm_step")
+        return heat, cell, hide
+
+    def clip(self, frames: torch.Tensor, centermaps: torch.Tensor, out=None):
+        """The whole clip: frames (B, T, 3, H, W), centermaps (B, T, 1, H, W) -> heats (B, T, K+1, h, w) and the last frame's cell,
+        hide (B, K+2, h, w).  T is the plan's `frames`."""
+        B, T, H, W, h, w, K = self.batch, self.frames, self.height, self.width, self.out_height, self.out_width, self.num_classes
+        x = self._input(frames, (B, T, 3, H, W), "clip")
+        cm = self._input(centermaps, (B, T, 1, H, W), "centre maps")
+        heat, cell, hide = self._outs(out, [(B, T, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
+        ws, nbytes = self._ws()
+        _C.check(_C.lib().up_unipose_lstm_clip(self._plan, x.data_ptr(), cm.data_ptr(), heat.data_ptr(), cell.data_ptr(),
+                                               hide.data_ptr(), ws, nbytes, self._stream()), "unipose_lstm_clip")
+        return heat, cell, hide
+
+    def close(self):
+        if self._plan:
+            _C.lib().up_unipose_lstm_plan_destroy(self._plan)
             self._plan = C.c_void_p()
 
     def __del__(self):
