@@ -452,6 +452,21 @@ int up_lstm_bwd(const float* gates, int ldg, const float* cprev, int ldc, const 
 int up_heatmap_argmax(const float* hm, int B, int J, int H, int W,
                       int32_t* idx, float* preds_xy, float* maxvals, void* stream);
 
+/* ---- heat-map decode: up-sampling + argmax without the up-sampled maps (ABI 10 addition) ----
+ * The outputs of up_heatmap_argmax for B x J maps of H x W AS IF they had been up-sampled to P x Q by up_bilinear_fwd first
+ * (the reference's full-resolution mode, model/unipose.py:31-32, followed by get_max_preds): idx = p * Q + q on the P x Q grid
+ * (may be NULL), preds_xy (B,J,2) zeroed where max <= 0, maxvals (B,J); NaN wins, the lowest flat index wins ties.  Every fine
+ * value is computed with the arithmetic of up_bilinear_fwd, so the result equals the composition bit for bit; P == H and
+ * Q == W reads the maps as they are (= up_heatmap_argmax).  The fine grid is never written: one workgroup per map, the coarse
+ * map in LDS where it fits (up to 12288 values), else read through L2.
+ * A map is addressed by three element strides, value (b, j, pixel i) at hm[b * stride_b + j * stride_j + i * stride_p]:
+ *   NHWC as a convolution leaves it (ld physical channels): stride_b = H * W * ld, stride_j = 1, stride_p = ld;
+ *   NCHW as the models and the video entries return it:     stride_b = J * H * W,  stride_j = H * W, stride_p = 1.
+ * UP_ERR_INVALID (nothing launched): null hm / preds_xy / maxvals, a size or a stride <= 0, P < H or Q < W (down-sampling is
+ * not a reference use), P * Q or the offset of the last element beyond the int32 range. */
+int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W,
+                      int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream);
+
 /* ---- training targets and input normalisation (the step BEFORE the path) ----
  * up_make_heatmaps: lsp_lspet_data.py:224-236 / mpii_data.py:165-175.  kpt_xy (B,K,2) float64 pixel coordinates of the
  * input image; joint k of sample b is centred at int(coordinate) / stride on the H x W map; values
@@ -500,7 +515,17 @@ int up_box_argmax(const float* maps, int C, int H, int W, const int32_t* boxes, 
  * Convolution names are the reference's state_dict prefixes ("backbone.layer3.11.conv2", "wasp.aspp2.atrous_conv",
  * "decoder.last_conv.8"); a parameter that is applied twice (wasp.conv2, wasp.py:72-80) appears twice, setting it once suffices.
  * Launches and descriptors are those of the drop-in module's folded inference forward: equal bits.  Training has no
- * whole-graph entry (it runs through autograd). */
+ * whole-graph entry (it runs through autograd).
+ * Two more programs run over the same weights and the same workspace (up_unipose_plan_workspace() covers the largest of the
+ * three; the full-resolution one needs a (batch, H, W, out_channels rounded up to 4) fp32 tensor more than the trunk):
+ *   up_unipose_forward_upsampled  the module's forward at stride != 8 (model/unipose.py:31-32): the heat-maps up-sampled to the
+ *                                 input size (up_bilinear_fwd), written NCHW (batch, out_channels, H, W).  Equal bits again.
+ *   up_unipose_keypoints          the trunk, then up_heatmap_decode straight from the NHWC output of decoder.last_conv.8: no layout
+ *                                 pass, no up-sampled tensor.  out_h x out_w is the heat-map size ceil(H/8) x ceil(W/8) (what
+ *                                 up_heatmap_argmax gives on up_unipose_forward's result) or the input size H x W (... on
+ *                                 up_unipose_forward_upsampled's); any other size is UP_ERR_INVALID.  idx (may be NULL), preds_xy,
+ *                                 maxvals: (batch, out_channels[, 2]); with the box head all out_channels are decoded, the
+ *                                 caller slices. */
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
     int32_t batch, height, width;   /* input (batch, 3, height, width) */
@@ -516,6 +541,10 @@ int up_unipose_plan_set_conv(up_unipose_plan* plan, int i, const float* w_oihw, 
 size_t up_unipose_plan_workspace(const up_unipose_plan* plan);
 int up_unipose_forward(up_unipose_plan* plan, const float* x_nchw, float* heat_nchw, void* workspace, size_t workspace_bytes,
                        void* stream);
+int up_unipose_forward_upsampled(up_unipose_plan* plan, const float* x_nchw, float* heat_nchw, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int up_unipose_keypoints(up_unipose_plan* plan, const float* x_nchw, int out_h, int out_w, int32_t* idx, float* preds_xy,
+                         float* maxvals, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- whole-clip and per-frame inference entry of UniPose-LSTM (ABI 10 additions) ----------------------------------------
  * The video network (model/uniposeLSTM.py:67-138: the image trunk with the video WASP, ConvLSTM, five-convolution head) with
@@ -532,7 +561,10 @@ int up_unipose_forward(up_unipose_plan* plan, const float* x_nchw, float* heat_n
  * h = ceil(H / 8) must equal the pooled centre map's (H - 7) / 8 + 1, i.e. H % 8 (and W % 8) in {0, 7}: create refuses the rest.
  * Convolution names are the reference's state_dict prefixes: the trunk's (wasp.conv2 twice; the video WASP's
  * wasp.global_avg_pool.1 has no bias), lstm_0.conv_{g,i,o}_lstm, lstm.conv_{g,i,o,f}{x,h}_lstm and conv1 .. conv5.  The plan
- * stacks the gate weights itself once all parts of a cell are set; a forward call while any is unset fails ("never set"). */
+ * stacks the gate weights itself once all parts of a cell are set; a forward call while any is unset fails ("never set").
+ * Both forms return heat-maps, on the h x w grid only (the reference's video model stores `stride` and never up-samples).  For
+ * key points, decode them with up_heatmap_decode on the NCHW output: T * B * (K+1) maps in one launch, stride_b = (K+1) * h * w,
+ * stride_j = h * w, stride_p = 1, and P x Q = h x w or an up-sampled grid. */
 typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
 typedef struct {
     int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */

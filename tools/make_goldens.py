@@ -627,6 +627,35 @@ def g16_trajectory(name="g16_adam_3steps_b8_128.npz", K=16, B=8, size=128, steps
     save(name, **arrs, meta=np.array([K, wseed, xseed, tseed, B, size, steps]))
 
 
+def g17_decode_full_res():
+    """G17: the reference's full-resolution decode of its own heat-maps: F.interpolate(bilinear, align_corners=True) to the input
+    size (model/unipose.py:31-32) followed by get_max_preds (utils/evaluate.py, loaded by path like G6).  The maps are those of
+    the fixtures G1 (2 x 15, -> 368 x 368), G10 (17, -> 736 x 736) and G5 heat0 .. heat3 (4 x 14, -> 368 x 368): 103 maps.  G5 heat4
+    stays out: one of its maps has an exact tie between its two best up-sampled values, so its index depends on the tie rule and
+    not on the arithmetic.  Stored: idx, preds, maxvals per group (data only); the tests read the maps from G1 / G10 / G5."""
+    import torch.nn.functional as F
+    spec = importlib.util.spec_from_file_location("ref_evaluate", os.path.join(REF, "utils", "evaluate.py"))
+    ev = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ev)
+    g5 = np.load(os.path.join(OUT, "g5_lstm_368.npz"))
+    groups = {"g1": (np.load(os.path.join(OUT, "g1_eval_368.npz"))["out"], 368),
+              "g10": (np.load(os.path.join(OUT, "g10_eval_736.npz"))["out"], 736),
+              "g5": (np.concatenate([g5[f"heat{j}"].reshape(1, 14, 46, 46) for j in range(4)], 0), 368)}
+    res, gaps = {}, []
+    for name, (hm, size) in groups.items():
+        up = F.interpolate(torch.from_numpy(hm), size=(size, size), mode="bilinear", align_corners=True)
+        preds, maxvals = ev.get_max_preds(up.numpy())
+        flat = up.reshape(up.shape[0], up.shape[1], -1)
+        top2 = flat.topk(2, dim=2).values
+        gaps.append((top2[..., 0] - top2[..., 1]).reshape(-1))
+        res["idx_" + name] = flat.argmax(2).numpy().astype(np.int32)
+        res["preds_" + name] = preds.astype(np.float32)
+        res["maxvals_" + name] = maxvals.astype(np.float32)
+    gaps = torch.cat(gaps)
+    print("g17:", gaps.numel(), "maps, smallest top-2 gap of the up-sampled maps", float(gaps.min()))
+    save("g17_decode_full_res.npz", **res, sizes=np.array([368, 736, 368]))
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -640,9 +669,9 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
-               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory)
+               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res)
     for w in which:
         fns[w]()

@@ -142,6 +142,7 @@ SIGNATURES = {
     "up_lstm_fwd": (_i, [_p, _i, _p, _i, _p, _p, _i, _i64, _i, _p]),
     "up_lstm_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _i, _p]),
     "up_heatmap_argmax": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "up_heatmap_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "up_make_heatmaps": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p]),
     "up_make_gaussian_maps": (_i, [_p, _i, _i, _i, C.c_double, _p, _p]),
     "up_normalize_image": (_i, [_p, _i, _i, _i, _i, _f, _f, _p, _p]),
@@ -156,6 +157,8 @@ SIGNATURES = {
     "up_unipose_plan_set_conv": (_i, [_p, _i, _p, _p, _p]),
     "up_unipose_plan_workspace": (_sz, [_p]),
     "up_unipose_forward": (_i, [_p, _p, _p, _p, _sz, _p]),
+    "up_unipose_forward_upsampled": (_i, [_p, _p, _p, _p, _sz, _p]),
+    "up_unipose_keypoints": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_clip_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),

@@ -11,6 +11,9 @@
 // The launches, their order, their descriptors and their epilogues are exactly those of the drop-in module's folded inference
 // forward (unipose_amd/unipose.py + modules.py after checkpoint.load_folded), so the two produce equal bits
 // (tests/test_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
+// The image plan keeps three programs over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
+// input size as the module does at stride != 8 (up_unipose_forward_upsampled), and the joints decoded straight from the NHWC
+// output of the last convolution (up_unipose_keypoints -> up_heatmap_decode; tests/test_heat_decode_*.py).
 //
 // The video network UniPose-LSTM (model/uniposeLSTM.py) has its entry here too (up_unipose_lstm_*, ABI 10 additions): the same
 // trunk builder with the video WASP, then the centre-map hand-over, the ConvLSTM cell and the head — per frame with the caller's
@@ -68,6 +71,7 @@ struct Conv {
 };
 enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW,
+    DECODE,                // key points straight from the NHWC heat-maps (up_heatmap_decode), on the grid the call names
     // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL
 };
@@ -333,7 +337,12 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     return p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, out_channels, 1, 1, 0, 1, 0, true, Ref(), heat);
 }
 
-static int build(Plan& p, const up_unipose_config& c) {
+// One program of the image plan over one weight store (like the video plan's LstmForm below).  HEAT_MAPS: the module's forward at
+// stride 8; UPSAMPLED: at stride != 8, the heat-maps bilinearly up-sampled to the input size before the layout pass
+// (model/unipose.py:31-32; unipose_amd/unipose.py forward); KEYPOINTS: the trunk, then up_heatmap_decode on its NHWC output.
+enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS };
+
+static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
     const int n = c.batch;
     int h = c.height, w = c.width;
     // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC)
@@ -348,6 +357,27 @@ static int build(Plan& p, const up_unipose_config& c) {
         p.push(op);
     }
     x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
+    if (form == KEYPOINTS) {
+        Op op;
+        op.kind = DECODE;
+        op.in = x;
+        op.n = n; op.c = c.out_channels;
+        p.push(op);
+        p.layout();
+        return UP_OK;
+    }
+    if (form == UPSAMPLED) {
+        const int ld = p.tensors[x.id].c;
+        Ref up;
+        up.id = p.tensor(n, c.height, c.width, ld);
+        Op op;
+        op.kind = BILINEAR;
+        op.in = x; op.out = up;
+        op.n = n;
+        op.a = h; op.b = w; op.c = ld; op.e = c.height * 65536 + c.width;
+        p.push(op);
+        x = up;
+    }
     {
         Op op;
         op.kind = TO_NCHW;
@@ -482,6 +512,10 @@ struct Io {
     float* heat = nullptr;
     float* cell = nullptr;
     float* hide = nullptr;
+    int dec_h = 0, dec_w = 0;        // DECODE: the grid, and the three outputs of up_heatmap_decode
+    int32_t* idx = nullptr;
+    float* preds = nullptr;
+    float* maxvals = nullptr;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -528,6 +562,10 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             if (io.out(op.ext))
                 e = up_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.out(op.ext), op.n, op.c, T_(op.in).h, T_(op.in).w, stream);
             break;
+        case DECODE:
+            e = up_heatmap_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c,
+                                  T_(op.in).h, T_(op.in).w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
+            break;
         case POOL:
             e = up_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.a, op.b, T_(op.out).h, T_(op.out).w, stream);
             break;
@@ -563,7 +601,9 @@ using up::plan::Plan;
 
 struct up_unipose_plan {
     up_unipose_config cfg;
-    Plan p;
+    Plan p;                    // HEAT_MAPS; its convolutions are the listed ones and own the weight store
+    Plan up, kp;               // UPSAMPLED, KEYPOINTS: the same trunk, so the same convolutions in the same order
+    size_t ws_bytes = 0;       // the largest of the three
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
@@ -575,9 +615,13 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
-    if (int e = up::plan::build(pl->p, pl->cfg)) {
-        delete pl;
-        return e;
+    Plan* const progs[3] = {&pl->p, &pl->up, &pl->kp};
+    for (int f = 0; f < 3; ++f) {
+        if (int e = up::plan::build(*progs[f], pl->cfg, static_cast<plan::ImageForm>(f))) {
+            delete pl;
+            return e;
+        }
+        pl->ws_bytes = std::max(pl->ws_bytes, progs[f]->ws_bytes);
     }
     // plan-owned device memory: one forward weight image (+ bias) per DISTINCT parameter (wasp.conv2 is applied twice)
     for (size_t i = 0; i < pl->p.convs.size(); ++i) {
@@ -596,6 +640,11 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
             UP_REQUIRE(false, UP_ERR_INVALID, "unipose_plan_create: out of device memory");
         }
     }
+    for (Plan* other : {&pl->up, &pl->kp})
+        for (size_t i = 0; i < other->convs.size(); ++i) {
+            other->convs[i].w_fwd = pl->p.convs[i].w_fwd;
+            other->convs[i].bias = pl->p.convs[i].bias;
+        }
     *out = pl;
     return UP_OK;
 }
@@ -640,19 +689,52 @@ extern "C" int up_unipose_plan_set_conv(up_unipose_plan* pl, int i, const float*
     return UP_OK;
 }
 
-extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return pl ? pl->p.ws_bytes : 0; }
+extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return pl ? pl->ws_bytes : 0; }
+
+static int image_ready(const up_unipose_plan* pl, const Plan& prog, const void* workspace, size_t ws_bytes, const char* what) {
+    for (const plan::Conv& cv : pl->p.convs)
+        UP_REQUIRE(cv.set, UP_ERR_INVALID, "%s: weights of %s were never set (up_unipose_plan_set_conv)", what, cv.name.c_str());
+    UP_REQUIRE(ws_bytes >= prog.ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_INVALID,
+               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, prog.ws_bytes, ws_bytes);
+    return UP_OK;
+}
 
 extern "C" int up_unipose_forward(up_unipose_plan* pl, const float* x_nchw, float* heat_nchw, void* workspace, size_t ws_bytes,
                                   void* stream) {
     UP_REQUIRE(pl && x_nchw && heat_nchw && workspace, UP_ERR_INVALID, "unipose_forward: null argument");
-    for (const plan::Conv& cv : pl->p.convs)
-        UP_REQUIRE(cv.set, UP_ERR_INVALID, "unipose_forward: weights of %s were never set (up_unipose_plan_set_conv)", cv.name.c_str());
-    UP_REQUIRE(ws_bytes >= pl->p.ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_INVALID,
-               "unipose_forward: workspace of %zu bytes (256-byte aligned) needed, got %zu", pl->p.ws_bytes, ws_bytes);
+    if (int e = image_ready(pl, pl->p, workspace, ws_bytes, "unipose_forward")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.heat = heat_nchw;
     return plan::run(pl->p, io, static_cast<unsigned char*>(workspace), stream, "unipose_forward");
+}
+
+extern "C" int up_unipose_forward_upsampled(up_unipose_plan* pl, const float* x_nchw, float* heat_nchw, void* workspace,
+                                            size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && heat_nchw && workspace, UP_ERR_INVALID, "unipose_forward_upsampled: null argument");
+    if (int e = image_ready(pl, pl->up, workspace, ws_bytes, "unipose_forward_upsampled")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.heat = heat_nchw;
+    return plan::run(pl->up, io, static_cast<unsigned char*>(workspace), stream, "unipose_forward_upsampled");
+}
+
+extern "C" int up_unipose_keypoints(up_unipose_plan* pl, const float* x_nchw, int out_h, int out_w, int32_t* idx, float* preds_xy,
+                                    float* maxvals, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_keypoints: null argument");
+    const plan::Tensor& heat = pl->kp.tensors[pl->kp.ops.back().in.id];
+    UP_REQUIRE((out_h == heat.h && out_w == heat.w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
+               "unipose_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h, out_w,
+               heat.h, heat.w, pl->cfg.height, pl->cfg.width);
+    if (int e = image_ready(pl, pl->kp, workspace, ws_bytes, "unipose_keypoints")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.dec_h = out_h;
+    io.dec_w = out_w;
+    io.idx = idx;
+    io.preds = preds_xy;
+    io.maxvals = maxvals;
+    return plan::run(pl->kp, io, static_cast<unsigned char*>(workspace), stream, "unipose_keypoints");
 }
 
 // ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------

@@ -181,6 +181,40 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const TI* dy, int lddy
 }
 
 // ---- bilinear, align_corners=True ----------------------------------------------------------
+// The two taps of output sample `o` (scale s, `n` input samples) with their weights, and the blend of the four neighbours
+//     lh0 * (lw0 * a00 + lw1 * a01) + lh1 * (lw0 * a10 + lw1 * a11).
+// bilinear_fwd_kernel and decode_kernel both go through these two: up_heatmap_decode promises the bits of up_bilinear_fwd.  Left
+// to the compiler, the contraction of these expressions to FMAs depends on the code around them (in bilinear_fwd_kernel it came
+// out differently for the even and the odd channels of a float4, in a scalar loop differently again), so the roundings are
+// spelled out: they are the ones bilinear_fwd_kernel has always had on gfx950 (read off its ISA; its results are unchanged).
+//   l1 = fma(s, o, -i0)                                                             (not the rounded product s * o minus i0)
+//   even channel: t = fma(lw0, left, lw1 * right), result fma(lh1, t1, lh0 * t0)
+//   odd channel:  t = fma(lw1, right, lw0 * left), result fma(lh0, t0, lh1 * t1)
+struct BilTap {
+    int i0, i1;
+    float l0, l1;
+};
+__device__ __forceinline__ BilTap bil_tap(float s, int o, int n) {
+    BilTap t;
+    const float fo = (float)o;
+    t.i0 = (int)__fmul_rn(s, fo);
+    t.i1 = t.i0 < n - 1 ? t.i0 + 1 : t.i0;
+    t.l1 = __fmaf_rn(s, fo, -(float)t.i0);
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+template <int ODD>
+__device__ __forceinline__ float bil_mix(float lh0, float lh1, float lw0, float lw1, float a00, float a01, float a10,
+                                         float a11) {
+    if (ODD) {
+        const float t0 = __fmaf_rn(lw1, a01, __fmul_rn(lw0, a00));
+        const float t1 = __fmaf_rn(lw1, a11, __fmul_rn(lw0, a10));
+        return __fmaf_rn(lh0, t0, __fmul_rn(lh1, t1));
+    }
+    const float t0 = __fmaf_rn(lw0, a00, __fmul_rn(lw1, a01));
+    const float t1 = __fmaf_rn(lw0, a10, __fmul_rn(lw1, a11));
+    return __fmaf_rn(lh1, t1, __fmul_rn(lh0, t0));
+}
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_fwd_kernel(const T* x, int ldx, T* y, int ldy, int H, int W,
                                                            int C4, int P, int Q, float sh, float sw, int64_t total,
@@ -192,20 +226,17 @@ __global__ void __launch_bounds__(256) bilinear_fwd_kernel(const T* x, int ldx, 
         int q = (int)pix - (int)t * Q;
         uint32_t n = fdiv(t, fP);
         int p = (int)t - (int)n * P;
-        float fh = sh * p, fw = sw * q;
-        int h0 = (int)fh, w0 = (int)fw;
-        int h1 = h0 < H - 1 ? h0 + 1 : h0, w1 = w0 < W - 1 ? w0 + 1 : w0;
-        float lh1 = fh - h0, lw1 = fw - w0, lh0 = 1.f - lh1, lw0 = 1.f - lw1;
+        const BilTap th = bil_tap(sh, p, H), tw = bil_tap(sw, q, W);
         const T* b = x + (size_t)n * H * W * ldx + c;
-        float4 a00 = ld4<T>(b + (size_t)(h0 * W + w0) * ldx);
-        float4 a01 = ld4<T>(b + (size_t)(h0 * W + w1) * ldx);
-        float4 a10 = ld4<T>(b + (size_t)(h1 * W + w0) * ldx);
-        float4 a11 = ld4<T>(b + (size_t)(h1 * W + w1) * ldx);
+        float4 a00 = ld4<T>(b + (size_t)(th.i0 * W + tw.i0) * ldx);
+        float4 a01 = ld4<T>(b + (size_t)(th.i0 * W + tw.i1) * ldx);
+        float4 a10 = ld4<T>(b + (size_t)(th.i1 * W + tw.i0) * ldx);
+        float4 a11 = ld4<T>(b + (size_t)(th.i1 * W + tw.i1) * ldx);
         float4 o;
-        o.x = lh0 * (lw0 * a00.x + lw1 * a01.x) + lh1 * (lw0 * a10.x + lw1 * a11.x);
-        o.y = lh0 * (lw0 * a00.y + lw1 * a01.y) + lh1 * (lw0 * a10.y + lw1 * a11.y);
-        o.z = lh0 * (lw0 * a00.z + lw1 * a01.z) + lh1 * (lw0 * a10.z + lw1 * a11.z);
-        o.w = lh0 * (lw0 * a00.w + lw1 * a01.w) + lh1 * (lw0 * a10.w + lw1 * a11.w);
+        o.x = bil_mix<0>(th.l0, th.l1, tw.l0, tw.l1, a00.x, a01.x, a10.x, a11.x);
+        o.y = bil_mix<1>(th.l0, th.l1, tw.l0, tw.l1, a00.y, a01.y, a10.y, a11.y);
+        o.z = bil_mix<0>(th.l0, th.l1, tw.l0, tw.l1, a00.z, a01.z, a10.z, a11.z);
+        o.w = bil_mix<1>(th.l0, th.l1, tw.l0, tw.l1, a00.w, a01.w, a10.w, a11.w);
         st4(y + (size_t)pix * ldy + c, o);
     }
 }
@@ -470,6 +501,79 @@ __global__ void __launch_bounds__(256) argmax_kernel(const float* hm, int maps, 
         float keep = bv > 0.f ? 1.f : 0.f;
         preds[map * 2] = (float)(bi % W) * keep;
         preds[map * 2 + 1] = (float)(bi / W) * keep;
+        maxvals[map] = bv;
+    }
+}
+
+// ---- heat-map decode: the argmax of the maps AS IF up-sampled to P x Q by up_bilinear_fwd; one workgroup per (b, j) map ------
+// The fine grid is never written.  Every thread evaluates the fine points i = tid, tid + 256, ... with the arithmetic of
+// bilinear_fwd_kernel (bil_tap / bil_mix) from the coarse map — staged in LDS (STAGE), or read from global memory where it does
+// not fit (it stays in L2) — and keeps (value, index); then the wave ladder of argmax_kernel and the four waves through LDS.
+// am_better is a total order (NaN first, then the value, then the lowest index), so the order of the reduction does not matter.
+// P == H and Q == W: no interpolation, the values are read as they are (never staged: each is read once).  A map is addressed
+// by three strides: NHWC as the convolutions leave it (sj = 1, sp = ld, pad channels skipped) or NCHW (sj = H * W, sp = 1).
+constexpr int DECODE_LDS = 12288;   // floats: 48 KB of the 64 KB static LDS limit (46 x 46 = 8.5 KB, 92 x 92 = 34 KB fit)
+template <bool STAGE>
+__global__ void __launch_bounds__(256) decode_kernel(const float* hm, int64_t sb, int64_t sj, int64_t sp, int J, int H, int W,
+                                                     int P, int Q, float sh, float sw, FastDiv fQ, int32_t* idx, float* preds,
+                                                     float* maxvals) {
+    __shared__ float tile[STAGE ? DECODE_LDS : 1];
+    __shared__ float red_v[4];
+    __shared__ int red_i[4];
+    const int map = blockIdx.x, tid = threadIdx.x;
+    const int b = map / J, j = map - b * J;
+    const float* src = hm + b * sb + j * sj;
+    const bool interp = P != H || Q != W;
+    const bool odd = j & 1;          // map j is channel j of the tensor up_bilinear_fwd would have run on
+    if (STAGE) {
+        for (int i = tid; i < H * W; i += 256) tile[i] = src[i * sp];
+        __syncthreads();
+    }
+    auto at = [&](int k) -> float { return STAGE ? tile[k] : src[k * sp]; };
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    const int PQ = P * Q;
+    for (int i = tid; i < PQ; i += 256) {
+        float v;
+        if (interp) {
+            const int p = (int)fdiv((uint32_t)i, fQ), q = i - p * Q;
+            const BilTap th = bil_tap(sh, p, H), tw = bil_tap(sw, q, W);
+            const float a00 = at(th.i0 * W + tw.i0), a01 = at(th.i0 * W + tw.i1), a10 = at(th.i1 * W + tw.i0),
+                        a11 = at(th.i1 * W + tw.i1);
+            v = odd ? bil_mix<1>(th.l0, th.l1, tw.l0, tw.l1, a00, a01, a10, a11)
+                    : bil_mix<0>(th.l0, th.l1, tw.l0, tw.l1, a00, a01, a10, a11);
+        } else {
+            v = src[i * sp];
+        }
+        if (am_better(v, i, bv, bi)) {
+            bv = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ov = __shfl_down(bv, off);
+        int oi = __shfl_down(bi, off);
+        if (am_better(ov, oi, bv, bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    if ((tid & 63) == 0) {
+        red_v[tid >> 6] = bv;
+        red_i[tid >> 6] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < 4; ++k)
+            if (am_better(red_v[k], red_i[k], bv, bi)) {
+                bv = red_v[k];
+                bi = red_i[k];
+            }
+        if (idx) idx[map] = bi;
+        float keep = bv > 0.f ? 1.f : 0.f;
+        preds[map * 2] = (float)(bi % Q) * keep;
+        preds[map * 2 + 1] = (float)(bi / Q) * keep;
         maxvals[map] = bv;
     }
 }
@@ -951,6 +1055,29 @@ extern "C" int up_heatmap_argmax(const float* hm, int B, int J, int H, int W, in
     hipLaunchKernelGGL(argmax_kernel, dim3(cdiv(maps, 4)), dim3(256), 0, as_stream(stream), hm, maps, H * W, W, idx,
                        preds_xy, maxvals);
     return check_launch("heatmap_argmax");
+}
+
+extern "C" int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H,
+                                 int W, int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream) {
+    UP_REQUIRE(hm && preds_xy && maxvals, UP_ERR_INVALID, "heatmap_decode: null argument");
+    UP_REQUIRE(B > 0 && J > 0 && H > 0 && W > 0 && stride_b > 0 && stride_j > 0 && stride_p > 0, UP_ERR_INVALID,
+               "heatmap_decode: %d x %d maps of %d x %d, strides %lld / %lld / %lld", B, J, H, W, (long long)stride_b,
+               (long long)stride_j, (long long)stride_p);
+    UP_REQUIRE(P >= H && Q >= W, UP_ERR_INVALID, "heatmap_decode: %d x %d -> %d x %d (down-sampling is not decoded)", H, W, P, Q);
+    const int64_t lim = INT32_MAX;
+    UP_REQUIRE((int64_t)P * Q <= lim && (int64_t)B * J <= lim && (int64_t)H * W <= lim && stride_b <= lim && stride_j <= lim &&
+                   stride_p <= lim && (B - 1) * stride_b <= lim && (J - 1) * stride_j <= lim && ((int64_t)H * W - 1) * stride_p <= lim &&
+                   (B - 1) * stride_b + (J - 1) * stride_j + ((int64_t)H * W - 1) * stride_p <= lim,
+               UP_ERR_INVALID, "heatmap_decode: %d x %d maps of %d x %d -> %d x %d: an index beyond the int32 range", B, J, H, W, P, Q);
+    const dim3 grid(B * J), block(256);
+    const float sh = ac_scale(H, P), sw = ac_scale(W, Q);     // as up_bilinear_fwd computes them
+    if ((P != H || Q != W) && H * W <= DECODE_LDS)
+        hipLaunchKernelGGL(decode_kernel<true>, grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P, Q, sh,
+                           sw, make_fastdiv(Q), idx, preds_xy, maxvals);
+    else
+        hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P, Q, sh,
+                           sw, make_fastdiv(Q), idx, preds_xy, maxvals);
+    return check_launch("heatmap_decode");
 }
 
 extern "C" int up_make_heatmaps(const double* kpt_xy, int B, int K, int H, int W, double stride, double sigma,

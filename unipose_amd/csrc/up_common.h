@@ -4,6 +4,9 @@
 #ifdef UP_EMU
 // tests/emu/hip_emu.h (force-included by the CPU emulation build used ONLY by tests) provides the
 // HIP surface: threadIdx/blockIdx, __shared__, __syncthreads, hipLaunchKernelGGL, MFMA, shuffles.
+// The explicitly rounded float intrinsics: the host build contracts nothing anywhere, so the fused form is the plain one there.
+static inline float __fmul_rn(float a, float b) { return a * b; }
+static inline float __fmaf_rn(float a, float b, float c) { return a * b + c; }
 #else
 #include <hip/hip_runtime.h>
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -1787,6 +1787,44 @@ def heatmap_argmax(hm: torch.Tensor):
     return preds, mx, idx
 
 
+def _decode(t, strides, b, j, h, w, size):
+    if size is None:
+        size = (h, w)
+    p, q = int(size[0]), int(size[1])
+    idx = torch.empty((b, j), dtype=torch.int32, device=t.device)
+    preds = torch.empty((b, j, 2), dtype=torch.float32, device=t.device)
+    mx = torch.empty((b, j, 1), dtype=torch.float32, device=t.device)
+    _C.check(_C.lib().up_heatmap_decode(t.data_ptr(), *strides, b, j, h, w, p, q, idx.data_ptr(), preds.data_ptr(), mx.data_ptr(),
+                                        _stream(t)), "heatmap_decode")
+    return preds, mx, idx
+
+
+def heatmap_decode(hm: torch.Tensor, size=None):
+    """The key points of NCHW heat-maps (B, J, h, w) as the models return them: ``heatmap_argmax(hm)`` for ``size=None``; for
+    ``size=(P, Q)`` what ``heatmap_argmax`` gives on the maps up-sampled to P x Q (``Bilinear``, align_corners=True: the
+    reference's full-resolution mode, model/unipose.py:31-32) — bit for bit, without ever writing the up-sampled maps.
+    Returns (preds (B,J,2) float32 on the P x Q grid, maxvals (B,J,1) float32, idx (B,J) int32)."""
+    _dev_ok(hm)
+    if hm.dtype != torch.float32:
+        raise TypeError(f"heatmap_decode: float32 heat-maps, got {hm.dtype}")
+    hm = _dense(hm.detach())
+    b, j, h, w = hm.shape
+    return _decode(hm, (j * h * w, h * w, 1), b, j, h, w, size)
+
+
+def heatmap_decode_nhwc(x: torch.Tensor, channels: int, size=None):
+    """``heatmap_decode`` of the first `channels` channels of an NHWC activation (B, h, w, ld) as a convolution leaves it (pad
+    channels are skipped): no layout pass in between."""
+    _dev_ok(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"heatmap_decode_nhwc: float32 heat-maps, got {x.dtype}")
+    b, h, w, _ = x.shape
+    ld = _nhwc_ok(x)
+    if not 0 < channels <= x.shape[3]:
+        raise ValueError(f"heatmap_decode_nhwc: {channels} channels of a tensor with {x.shape[3]}")
+    return _decode(x.detach(), (h * w * ld, 1, ld), b, channels, h, w, size)
+
+
 def _as_f64(a, dev):
     t = torch.as_tensor(a, dtype=torch.float64).contiguous()
     t = t.to(dev) if dev is not None else t

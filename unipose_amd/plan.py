@@ -1,4 +1,5 @@
-"""``UniPosePlan`` — the image model's inference forward as ONE call into the C ABI (``up_unipose_forward``, ABI 9).
+"""``UniPosePlan`` — the image model's inference forward as ONE call into the C ABI (``up_unipose_forward``, ABI 9; at
+``stride != 8`` ``up_unipose_forward_upsampled``; key points instead of heat-maps: ``up_unipose_keypoints``).
 
 The reference's validation / test loops run ``heat = model(input)`` per batch (unipose.py:150-160).  A plan is built once
 from a model (any ``unipose`` with ``bbox`` or not, output stride 16 / 8): its BatchNorm layers are folded into the
@@ -9,6 +10,11 @@ and returns the heat-maps (the two slices of ``unipose(bbox=True)`` when the mod
     model = unipose("MPII", num_classes=16).cuda().eval(); model.load_state_dict(...)
     plan = UniPosePlan(model, batch=8, height=368, width=368)
     heat = plan(images)                      # equal bits to checkpoint.load_folded(...)(images)
+    preds, maxvals, idx = plan.keypoints(images)     # equal bits to ops.heatmap_argmax(heat), without the NCHW heat-maps
+
+A model built with ``stride != 8`` (the reference's full-resolution mode, model/unipose.py:31-32) gives the heat-maps up-sampled
+to the input size, as the module does; ``keypoints`` then decodes on that grid without ever writing the up-sampled maps
+(``up_heatmap_decode``).
 
 The launches are those of the drop-in module's folded forward, so the results agree bit for bit
 (tests/test_plan_emu.py, tests/test_plan_gpu.py).  Weights are captured at construction: call ``refresh(model)`` after
@@ -55,10 +61,10 @@ def _set_convs(plan, prefix, folded):
     del keep
 
 
-def _check_out(who, name, t, shape, dev):
-    if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+def _check_out(who, name, t, shape, dev, dtype=torch.float32):
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
         raise ValueError(f"{who}: `{name}` is {tuple(t.shape)} {t.dtype} on {t.device} (contiguous: {t.is_contiguous()}), "
-                         f"the plan writes a contiguous float32 {shape} on {dev}")
+                         f"the plan writes a contiguous {str(dtype).replace('torch.', '')} {shape} on {dev}")
     return t
 
 
@@ -66,10 +72,9 @@ class UniPosePlan:
     def __init__(self, model, batch: int, height: int, width: int):
         if model.training:
             raise ValueError("UniPosePlan captures the inference forward: call model.eval() first")
-        if getattr(model, "stride", 8) != 8:
-            raise NotImplementedError("UniPosePlan: stride != 8 (the extra 8x up-sampling of model/unipose.py:31-32) is not planned")
         if batch < 1 or height < 8 or width < 8:
             raise ValueError(f"UniPosePlan: batch {batch}, {height} x {width} input")
+        self.upsampled = getattr(model, "stride", 8) != 8      # model/unipose.py:31-32: heat-maps at the input size
         w0 = model.backbone.conv1.weight
         if not w0.is_cuda and not _C._ALLOW_HOST_POINTERS:
             raise _C.UniPoseHipError("UniPosePlan needs a CUDA(HIP) model; there is no CPU fallback")
@@ -85,7 +90,9 @@ class UniPosePlan:
         self.batch, self.height, self.width, self.out_channels = batch, height, width, out_channels
         # heat-map size: three ceil-halvings (7x7 stride-2 stem, 3x3 stride-2 max-pool, layer2's stride 2), the arithmetic of
         # plan.hip's build(): ceil(H / 8), NOT H // 8 — the two differ whenever H % 8 != 0 (a 52 x 52 input gives 7 x 7 maps)
-        self.out_height, self.out_width = (height - 1) // 8 + 1, (width - 1) // 8 + 1
+        self.map_height, self.map_width = (height - 1) // 8 + 1, (width - 1) // 8 + 1
+        # what plan(x) writes: the maps themselves, or (stride != 8) the maps up-sampled to the input size
+        self.out_height, self.out_width = (height, width) if self.upsampled else (self.map_height, self.map_width)
         self.workspace = torch.empty(max(L.up_unipose_plan_workspace(self._plan), 256) + 256, dtype=torch.uint8, device=self.device)
         self.refresh(model)
 
@@ -96,11 +103,14 @@ class UniPosePlan:
         """(re)load the weights: BatchNorm folded in float64 and rounded once, like checkpoint.fold_batchnorm / load_folded"""
         _set_convs(self, "up_unipose_plan", fold_batchnorm(model))
 
-    def __call__(self, x: torch.Tensor, out: torch.Tensor = None):
+    def _input(self, x):
         if tuple(x.shape) != (self.batch, 3, self.height, self.width) or x.dtype != torch.float32 or x.device != self.device:
             raise ValueError(f"UniPosePlan: input {tuple(x.shape)} {x.dtype} on {x.device}, planned for "
                              f"{(self.batch, 3, self.height, self.width)} float32 on {self.device}")
-        x = x.contiguous()
+        return x.contiguous()
+
+    def __call__(self, x: torch.Tensor, out: torch.Tensor = None):
+        x = self._input(x)
         shape = (self.batch, self.out_channels, self.out_height, self.out_width)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -109,11 +119,36 @@ class UniPosePlan:
                              f"the plan writes a contiguous float32 {shape} on {self.device}")
         ws = self.workspace
         off = (-ws.data_ptr()) % 256
-        _C.check(_C.lib().up_unipose_forward(self._plan, x.data_ptr(), out.data_ptr(), ws.data_ptr() + off, ws.numel() - off,
-                                             self._stream()), "unipose_forward")
+        forward = _C.lib().up_unipose_forward_upsampled if self.upsampled else _C.lib().up_unipose_forward
+        _C.check(forward(self._plan, x.data_ptr(), out.data_ptr(), ws.data_ptr() + off, ws.numel() - off, self._stream()),
+                 "unipose_forward_upsampled" if self.upsampled else "unipose_forward")
         if self.bbox:                   # model/unipose.py:34-35
             return out[:, 0:self.num_classes + 1], out[:, self.num_classes + 1:]
         return out
+
+    def keypoints(self, x: torch.Tensor, full_resolution: bool = None, out=None):
+        """get_max_preds (utils/evaluate.py:32-54) of the forward's heat-maps without writing them: (preds (B, C, 2) float32,
+        maxvals (B, C, 1) float32, idx (B, C) int32) for all C output channels (with the box head the caller slices) — equal bits
+        to ``ops.heatmap_argmax`` of the heat-maps.  full_resolution (default: the model's ``stride != 8``): on the grid of the
+        maps up-sampled to the input size, else on the maps' own.  `out`: a (preds, maxvals, idx) triple to write into."""
+        x = self._input(x)
+        if full_resolution is None:
+            full_resolution = self.upsampled
+        B, C_ = self.batch, self.out_channels
+        shapes = ((B, C_, 2), (B, C_, 1), (B, C_))
+        dtypes = (torch.float32, torch.float32, torch.int32)
+        if out is None:
+            out = tuple(torch.empty(s, dtype=d, device=self.device) for s, d in zip(shapes, dtypes))
+        elif len(out) != 3:
+            raise ValueError("UniPosePlan.keypoints: `out` is a (preds, maxvals, idx) triple")
+        preds, maxvals, idx = (_check_out("UniPosePlan.keypoints", n, t, s, self.device, d)
+                               for n, t, s, d in zip(("preds", "maxvals", "idx"), out, shapes, dtypes))
+        oh, ow = (self.height, self.width) if full_resolution else (self.map_height, self.map_width)
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        _C.check(_C.lib().up_unipose_keypoints(self._plan, x.data_ptr(), oh, ow, idx.data_ptr(), preds.data_ptr(), maxvals.data_ptr(),
+                                               ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_keypoints")
+        return preds, maxvals, idx
 
     def close(self):
         if self._plan:
@@ -151,8 +186,8 @@ class UniPoseLSTMPlan:
     def __init__(self, model, batch: int, height: int, width: int, frames: int = 1):
         if model.training:
             raise ValueError("UniPoseLSTMPlan captures the inference forward: call model.eval() first")
-        if getattr(model, "stride", 8) != 8:
-            raise NotImplementedError("UniPoseLSTMPlan: stride != 8 is not planned")
+        # model.stride is not looked at: the reference's video model stores it (model/uniposeLSTM.py:71) and never up-samples, and
+        # neither does the drop-in module (unipose_amd/uniposeLSTM.py).  Decode the heat-maps with ops.heatmap_decode(hm, size).
         if batch < 1 or frames < 1 or height < 8 or width < 8:
             raise ValueError(f"UniPoseLSTMPlan: batch {batch}, {frames} frames, {height} x {width} input")
         w0 = model.backbone.conv1.weight
