@@ -504,6 +504,33 @@ int up_peak_mask(const float* maps, int nmaps, int H, int W, uint8_t* mask, void
 int up_box_argmax(const float* maps, int C, int H, int W, const int32_t* boxes, int P, int ch0, int nch,
                   int32_t* out_hw, void* stream);
 
+/* ---- multi-person decode of a whole batch in one launch (ABI 10 addition) ----
+ * For every sample b what the reference's uniPose_kpts gives on maps[b:b+1], with nothing crossing to the host: one workgroup per
+ * sample lists the peaks (the rule of up_peak_mask) of the five box maps box_ch0 .. box_ch0+4 = centre, top-left, bottom-left,
+ * top-right, bottom-right in row-major order, walks the n centre peaks, and arg-maxes the joint channels joint_ch0 ..
+ * joint_ch0+njoints-1 inside every person's box (the order of up_box_argmax: NaN wins, the first maximum in the box's row-major
+ * order wins ties, a box of -inf only gives its first pixel).  The five maps are staged in LDS where 5 * H * W <= 12288 values,
+ * read through L2 otherwise.  The maps are addressed by three element strides exactly like up_heatmap_decode's (NHWC as a
+ * convolution leaves it, pad channels never read, or NCHW); C is the number of logical channels.
+ *   count[b]  = n, the number of centre peaks, always.
+ *   status[b] = UP_PERSONS_OVERFLOW when n > max_persons (nothing else is written for the sample); otherwise the first failure
+ *               of the reference's walk idx = 0 .. n-1, at each idx in its order: tl[idx] exists, br[idx] exists, the box rows
+ *               tl.row .. br.row, columns tl.col .. br.col (half-open) is non-empty, bl[idx] exists, tr[idx] exists — a missing
+ *               entry is UP_PERSONS_MISSING_CORNER (the reference's IndexError), an empty box UP_PERSONS_EMPTY_BOX (its
+ *               ValueError); the kpts rows of such a sample are unspecified.  A corner map with more than max_persons peaks is
+ *               no overflow: only its first n entries are ever used.  NaN in the five box maps is outside the contract.
+ *   kpts (B, max_persons, njoints + 5, 2) int32 = (x, y): with UP_PERSONS_OK person p < n gets the njoints joints, then centre,
+ *               tl, bl, tr, br.  Rows of persons >= n are not written.  A failing sample does not affect the others.
+ * max_persons bounds the LDS lists: 1 .. UP_PERSONS_CAP.
+ * UP_ERR_INVALID (nothing launched): a null pointer, a size or a stride <= 0, max_persons outside 1 .. UP_PERSONS_CAP, box_ch0 < 0
+ * or box_ch0 + 5 > C, joint_ch0 < 0, njoints < 1 or joint_ch0 + njoints > C, the offset of the last element or the size of kpts
+ * beyond the int32 range. */
+enum { UP_PERSONS_OK = 0, UP_PERSONS_MISSING_CORNER = 1, UP_PERSONS_EMPTY_BOX = 2, UP_PERSONS_OVERFLOW = 3 };
+enum { UP_PERSONS_CAP = 512 };
+int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int C, int H, int W,
+                      int box_ch0, int joint_ch0, int njoints, int max_persons, int32_t* count, int32_t* status, int32_t* kpts,
+                      void* stream);
+
 /* ---- whole-graph inference entry (ABI 9) ----------------------------------------------------------------------------
  * The UniPose image network (model/unipose.py:8-38: ResNet-101 + WASP + decoder) with every BatchNorm folded into its
  * convolution, as ONE call on one stream — what the reference's validation / test loops issue as `heat = model(input)`
@@ -516,8 +543,8 @@ int up_box_argmax(const float* maps, int C, int H, int W, const int32_t* boxes, 
  * "decoder.last_conv.8"); a parameter that is applied twice (wasp.conv2, wasp.py:72-80) appears twice, setting it once suffices.
  * Launches and descriptors are those of the drop-in module's folded inference forward: equal bits.  Training has no
  * whole-graph entry (it runs through autograd).
- * Two more programs run over the same weights and the same workspace (up_unipose_plan_workspace() covers the largest of the
- * three; the full-resolution one needs a (batch, H, W, out_channels rounded up to 4) fp32 tensor more than the trunk):
+ * Three more programs run over the same weights and the same workspace (up_unipose_plan_workspace() covers the largest of the
+ * four; the full-resolution one needs a (batch, H, W, out_channels rounded up to 4) fp32 tensor more than the trunk):
  *   up_unipose_forward_upsampled  the module's forward at stride != 8 (model/unipose.py:31-32): the heat-maps up-sampled to the
  *                                 input size (up_bilinear_fwd), written NCHW (batch, out_channels, H, W).  Equal bits again.
  *   up_unipose_keypoints          the trunk, then up_heatmap_decode straight from the NHWC output of decoder.last_conv.8: no layout
@@ -525,7 +552,12 @@ int up_box_argmax(const float* maps, int C, int H, int W, const int32_t* boxes, 
  *                                 up_heatmap_argmax gives on up_unipose_forward's result) or the input size H x W (... on
  *                                 up_unipose_forward_upsampled's); any other size is UP_ERR_INVALID.  idx (may be NULL), preds_xy,
  *                                 maxvals: (batch, out_channels[, 2]); with the box head all out_channels are decoded, the
- *                                 caller slices. */
+ *                                 caller slices.
+ *   up_unipose_persons            for a plan with the box head: the trunk, then up_persons_decode straight from the NHWC output of
+ *                                 decoder.last_conv.8, on the heat-maps' own grid (the one the reference decodes on): count, status
+ *                                 (batch), kpts (batch, max_persons, njoints + 5, 2) as documented there.  Channel arguments
+ *                                 outside out_channels, max_persons outside 1 .. UP_PERSONS_CAP or a null pointer are
+ *                                 UP_ERR_INVALID before anything is launched. */
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
     int32_t batch, height, width;   /* input (batch, 3, height, width) */
@@ -545,6 +577,8 @@ int up_unipose_forward_upsampled(up_unipose_plan* plan, const float* x_nchw, flo
                                  size_t workspace_bytes, void* stream);
 int up_unipose_keypoints(up_unipose_plan* plan, const float* x_nchw, int out_h, int out_w, int32_t* idx, float* preds_xy,
                          float* maxvals, void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_persons(up_unipose_plan* plan, const float* x_nchw, int box_ch0, int joint_ch0, int njoints, int max_persons,
+                       int32_t* count, int32_t* status, int32_t* kpts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- whole-clip and per-frame inference entry of UniPose-LSTM (ABI 10 additions) ----------------------------------------
  * The video network (model/uniposeLSTM.py:67-138: the image trunk with the video WASP, ConvLSTM, five-convolution head) with

@@ -149,6 +149,7 @@ SIGNATURES = {
     "up_pck_accuracy": (_i, [_p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     "up_peak_mask": (_i, [_p, _i, _i, _i, _p, _p]),
     "up_box_argmax": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
+    "up_persons_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "up_unipose_plan_create": (_i, [_p, C.POINTER(_p)]),
     "up_unipose_plan_destroy": (None, [_p]),
     "up_unipose_plan_num_convs": (_i, [_p]),
@@ -159,6 +160,7 @@ SIGNATURES = {
     "up_unipose_forward": (_i, [_p, _p, _p, _p, _sz, _p]),
     "up_unipose_forward_upsampled": (_i, [_p, _p, _p, _p, _sz, _p]),
     "up_unipose_keypoints": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_persons": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_clip_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),

@@ -11,9 +11,10 @@
 // The launches, their order, their descriptors and their epilogues are exactly those of the drop-in module's folded inference
 // forward (unipose_amd/unipose.py + modules.py after checkpoint.load_folded), so the two produce equal bits
 // (tests/test_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
-// The image plan keeps three programs over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
-// input size as the module does at stride != 8 (up_unipose_forward_upsampled), and the joints decoded straight from the NHWC
-// output of the last convolution (up_unipose_keypoints -> up_heatmap_decode; tests/test_heat_decode_*.py).
+// The image plan keeps four programs over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
+// input size as the module does at stride != 8 (up_unipose_forward_upsampled), the joints decoded straight from the NHWC
+// output of the last convolution (up_unipose_keypoints -> up_heatmap_decode; tests/test_heat_decode_*.py), and the persons of
+// the box head decoded from the same NHWC output (up_unipose_persons -> up_persons_decode; tests/test_persons_*.py).
 //
 // The video network UniPose-LSTM (model/uniposeLSTM.py) has its entry here too (up_unipose_lstm_*, ABI 10 additions): the same
 // trunk builder with the video WASP, then the centre-map hand-over, the ConvLSTM cell and the head — per frame with the caller's
@@ -72,6 +73,7 @@ struct Conv {
 enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW,
     DECODE,                // key points straight from the NHWC heat-maps (up_heatmap_decode), on the grid the call names
+    PERSONS,               // the multi-person decode straight from the NHWC heat-maps (up_persons_decode), on their own grid
     // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL
 };
@@ -339,8 +341,9 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
 
 // One program of the image plan over one weight store (like the video plan's LstmForm below).  HEAT_MAPS: the module's forward at
 // stride 8; UPSAMPLED: at stride != 8, the heat-maps bilinearly up-sampled to the input size before the layout pass
-// (model/unipose.py:31-32; unipose_amd/unipose.py forward); KEYPOINTS: the trunk, then up_heatmap_decode on its NHWC output.
-enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS };
+// (model/unipose.py:31-32; unipose_amd/unipose.py forward); KEYPOINTS: the trunk, then up_heatmap_decode on its NHWC output;
+// PERSONS_FORM: the trunk, then up_persons_decode on its NHWC output.
+enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM };
 
 static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
     const int n = c.batch;
@@ -357,9 +360,9 @@ static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
         p.push(op);
     }
     x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
-    if (form == KEYPOINTS) {
+    if (form == KEYPOINTS || form == PERSONS_FORM) {
         Op op;
-        op.kind = DECODE;
+        op.kind = form == KEYPOINTS ? DECODE : PERSONS;
         op.in = x;
         op.n = n; op.c = c.out_channels;
         p.push(op);
@@ -516,6 +519,10 @@ struct Io {
     int32_t* idx = nullptr;
     float* preds = nullptr;
     float* maxvals = nullptr;
+    int box_ch0 = 0, joint_ch0 = 0, njoints = 0, max_persons = 0;     // PERSONS: the arguments and outputs of up_persons_decode
+    int32_t* count = nullptr;
+    int32_t* status = nullptr;
+    int32_t* kpts = nullptr;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -566,6 +573,10 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             e = up_heatmap_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c,
                                   T_(op.in).h, T_(op.in).w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
             break;
+        case PERSONS:
+            e = up_persons_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c, T_(op.in).h,
+                                  T_(op.in).w, io.box_ch0, io.joint_ch0, io.njoints, io.max_persons, io.count, io.status, io.kpts, stream);
+            break;
         case POOL:
             e = up_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.a, op.b, T_(op.out).h, T_(op.out).w, stream);
             break;
@@ -602,8 +613,8 @@ using up::plan::Plan;
 struct up_unipose_plan {
     up_unipose_config cfg;
     Plan p;                    // HEAT_MAPS; its convolutions are the listed ones and own the weight store
-    Plan up, kp;               // UPSAMPLED, KEYPOINTS: the same trunk, so the same convolutions in the same order
-    size_t ws_bytes = 0;       // the largest of the three
+    Plan up, kp, ps;           // UPSAMPLED, KEYPOINTS, PERSONS_FORM: the same trunk, so the same convolutions in the same order
+    size_t ws_bytes = 0;       // the largest of the four
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
@@ -615,8 +626,8 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
-    Plan* const progs[3] = {&pl->p, &pl->up, &pl->kp};
-    for (int f = 0; f < 3; ++f) {
+    Plan* const progs[4] = {&pl->p, &pl->up, &pl->kp, &pl->ps};
+    for (int f = 0; f < 4; ++f) {
         if (int e = up::plan::build(*progs[f], pl->cfg, static_cast<plan::ImageForm>(f))) {
             delete pl;
             return e;
@@ -640,7 +651,7 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
             UP_REQUIRE(false, UP_ERR_INVALID, "unipose_plan_create: out of device memory");
         }
     }
-    for (Plan* other : {&pl->up, &pl->kp})
+    for (Plan* other : {&pl->up, &pl->kp, &pl->ps})
         for (size_t i = 0; i < other->convs.size(); ++i) {
             other->convs[i].w_fwd = pl->p.convs[i].w_fwd;
             other->convs[i].bias = pl->p.convs[i].bias;
@@ -735,6 +746,32 @@ extern "C" int up_unipose_keypoints(up_unipose_plan* pl, const float* x_nchw, in
     io.preds = preds_xy;
     io.maxvals = maxvals;
     return plan::run(pl->kp, io, static_cast<unsigned char*>(workspace), stream, "unipose_keypoints");
+}
+
+extern "C" int up_unipose_persons(up_unipose_plan* pl, const float* x_nchw, int box_ch0, int joint_ch0, int njoints, int max_persons,
+                                  int32_t* count, int32_t* status, int32_t* kpts, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && count && status && kpts && workspace, UP_ERR_INVALID, "unipose_persons: null argument");
+    const int C = pl->cfg.out_channels;
+    UP_REQUIRE(box_ch0 >= 0 && (int64_t)box_ch0 + 5 <= C, UP_ERR_INVALID, "unipose_persons: box channels %d..%lld, the plan has %d",
+               box_ch0, (long long)box_ch0 + 4, C);
+    UP_REQUIRE(joint_ch0 >= 0 && njoints >= 1 && (int64_t)joint_ch0 + njoints <= C, UP_ERR_INVALID,
+               "unipose_persons: %d joint channels from %d, the plan has %d", njoints, joint_ch0, C);
+    UP_REQUIRE(max_persons >= 1 && max_persons <= UP_PERSONS_CAP, UP_ERR_INVALID, "unipose_persons: max_persons %d (1..%d)", max_persons,
+               UP_PERSONS_CAP);
+    UP_REQUIRE((int64_t)pl->cfg.batch * max_persons * (njoints + 5) * 2 <= INT32_MAX, UP_ERR_INVALID,
+               "unipose_persons: %d persons of %d rows for %d samples: an index beyond the int32 range", max_persons, njoints + 5,
+               pl->cfg.batch);
+    if (int e = image_ready(pl, pl->ps, workspace, ws_bytes, "unipose_persons")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.box_ch0 = box_ch0;
+    io.joint_ch0 = joint_ch0;
+    io.njoints = njoints;
+    io.max_persons = max_persons;
+    io.count = count;
+    io.status = status;
+    io.kpts = kpts;
+    return plan::run(pl->ps, io, static_cast<unsigned char*>(workspace), stream, "unipose_persons");
 }
 
 // ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------

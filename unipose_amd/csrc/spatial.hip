@@ -582,37 +582,39 @@ __global__ void __launch_bounds__(256) decode_kernel(const float* hm, int64_t sb
 // Peaks of a map as the reference finds them: negatives clamped to 0, then `maximum_filter(3x3) == map` XOR the eroded
 // zero background (scipy, borders reflected / counted as background) — which is exactly: value > 0 and >= each of its
 // in-bounds 8 neighbours (plateaus mark every member).
-__global__ void __launch_bounds__(256) peak_mask_kernel(const float* maps, long long total, int H, int W, uint8_t* mask) {
-    long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int w = (int)(e % W);
-    const int h = (int)((e / W) % H);
-    const float v = maps[e];
+// The predicate itself, for pixel i = h * W + w of one map read through at(pixel): peak_mask_kernel and persons_kernel share it.
+template <typename At>
+__device__ __forceinline__ bool is_peak(At at, int i, int h, int w, int H, int W) {
+    const float v = at(i);
     bool peak = v > 0.f;
     for (int dh = -1; dh <= 1; ++dh)
         for (int dw = -1; dw <= 1; ++dw) {
             const int hh = h + dh, ww = w + dw;
             if (hh < 0 || ww < 0 || hh >= H || ww >= W) continue;
-            peak = peak && v >= maps[e + (long long)dh * W + dw];
+            peak = peak && v >= at(i + dh * W + dw);
         }
-    mask[e] = peak ? 1 : 0;
+    return peak;
+}
+__global__ void __launch_bounds__(256) peak_mask_kernel(const float* maps, long long total, int H, int W, uint8_t* mask) {
+    long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int w = (int)(e % W);
+    const int h = (int)((e / W) % H);
+    const float* m = maps + (e - ((long long)h * W + w));
+    mask[e] = is_peak([&](int k) -> float { return m[k]; }, h * W + w, h, w, H, W) ? 1 : 0;
 }
 // argmax of channels ch0 .. ch0+nch-1 inside one box per person: one wavefront per (person, channel); position
 // relative to the box, first maximum in the row-major order of the BOX (np.argmax of the sliced array)
-__global__ void __launch_bounds__(256) box_argmax_kernel(const float* maps, int H, int W, const int32_t* boxes, int P,
-                                                         int ch0, int nch, int32_t* out_hw) {
-    const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (job >= P * nch) return;
-    const int p = job / nch, c = job - p * nch;
-    const int r0 = boxes[p * 4], r1 = boxes[p * 4 + 1], c0 = boxes[p * 4 + 2], c1 = boxes[p * 4 + 3];
-    const int bw = c1 - c0, n = (r1 - r0) * bw;
-    const float* m = maps + (size_t)(ch0 + c) * H * W;
+// The reduction, by one whole wavefront: the index (row-major inside the box of bh x bw at (r0, c0)) of the first maximum of a
+// map read through at(row, col); the result is valid in lane 0.  box_argmax_kernel and persons_kernel share it.
+template <typename At>
+__device__ __forceinline__ int box_first_max(At at, int r0, int c0, int bh, int bw, int lane) {
+    const int n = bh * bw;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = lane; i < n; i += 64) {
         const int rr = i / bw, cc = i - rr * bw;
-        const float v = m[(size_t)(r0 + rr) * W + c0 + cc];
+        const float v = at(r0 + rr, c0 + cc);
         if (am_better(v, i, bv, bi)) {
             bv = v;
             bi = i;
@@ -627,10 +629,139 @@ __global__ void __launch_bounds__(256) box_argmax_kernel(const float* maps, int 
             bi = oi;
         }
     }
+    return bi == 0x7fffffff ? 0 : bi;   // a box of -inf only: np.argmax returns 0
+}
+__global__ void __launch_bounds__(256) box_argmax_kernel(const float* maps, int H, int W, const int32_t* boxes, int P,
+                                                         int ch0, int nch, int32_t* out_hw) {
+    const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (job >= P * nch) return;
+    const int p = job / nch, c = job - p * nch;
+    const int r0 = boxes[p * 4], r1 = boxes[p * 4 + 1], c0 = boxes[p * 4 + 2], c1 = boxes[p * 4 + 3];
+    const int bw = c1 - c0;
+    const float* m = maps + (size_t)(ch0 + c) * H * W;
+    const int bi = box_first_max([&](int r, int cc) -> float { return m[(size_t)r * W + cc]; }, r0, c0, r1 - r0, bw, lane);
     if (lane == 0) {
-        if (bi == 0x7fffffff) bi = 0;   // a box of -inf only: np.argmax returns 0
         out_hw[job * 2] = bi / bw;
         out_hw[job * 2 + 1] = bi - (bi / bw) * bw;
+    }
+}
+
+// ---- multi-person decode of a whole batch in one launch: one workgroup per sample (up_persons_decode) ---------------------------
+// What ops.uniPose_kpts does with up_peak_mask, torch.nonzero, host lists and up_box_argmax, for every sample, without the host.
+// Three phases, a barrier between them:
+//  1. ordered compaction: the five box maps (centre, tl, bl, tr, br; staged in LDS (STAGE) when 5 * H * W <= DECODE_LDS, read
+//     through L2 otherwise) are walked together in row-major chunks of 256 pixels.  Every thread tests its pixel in the five maps
+//     (is_peak); the five flags travel as 10-bit fields of two words (a chunk counts at most 256 per map) through one scan: inclusive
+//     suffix sums inside the wavefront with __shfl_down, the four wavefront totals through LDS, so
+//     slot = running base + peaks of earlier wavefronts + (total of this wavefront - suffix sum).  The first max_persons peaks of
+//     every map land in its LDS list as flat pixel indices, in row-major order; the running bases end as the true lengths.
+//  2. status walk: thread 0 walks the centre peaks in the reference's order of checks and publishes n and the status.
+//  3. box argmax: one wavefront per (person, joint) job with box_first_max, the joint maps read from global memory through the
+//     strides; then the centre and corner rows.
+constexpr int PERSONS_FIELD = 10;       // bits per map in the packed flags
+template <bool STAGE>
+__global__ void __launch_bounds__(256) persons_kernel(const float* maps, int64_t sb, int64_t sj, int64_t sp, int H, int W, FastDiv fW,
+                                                      int box_ch0, int joint_ch0, int njoints, int max_persons, int32_t* count,
+                                                      int32_t* status, int32_t* kpts) {
+    __shared__ float tile[STAGE ? DECODE_LDS : 1];
+    __shared__ int32_t list[5][UP_PERSONS_CAP];
+    __shared__ uint32_t wsum[2][4][2];                  // [chunk parity][wavefront][word]: one barrier per chunk is enough
+    __shared__ int s_n;
+    __shared__ int s_status;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int HW = H * W;
+    const float* src = maps + b * sb;
+    const float* box = src + box_ch0 * sj;
+    if (STAGE) {
+        for (int m = 0; m < 5; ++m)
+            for (int i = tid; i < HW; i += 256) tile[m * HW + i] = box[m * sj + i * sp];
+        __syncthreads();
+    }
+    int base[5] = {0, 0, 0, 0, 0};
+    for (int c0 = 0, par = 0; c0 < HW; c0 += 256, par ^= 1) {
+        const int i = c0 + tid;
+        uint32_t flag[2] = {0u, 0u};
+        if (i < HW) {
+            const int h = (int)fdiv((uint32_t)i, fW), w = i - h * W;
+#pragma unroll
+            for (int m = 0; m < 5; ++m) {
+                auto at = [&](int k) -> float { return STAGE ? tile[m * HW + k] : box[m * sj + k * sp]; };
+                if (is_peak(at, i, h, w, H, W)) flag[m / 3] |= 1u << (PERSONS_FIELD * (m % 3));
+            }
+        }
+        uint32_t suf[2] = {flag[0], flag[1]};           // -> peaks at lanes >= this one, per field
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t t0 = __shfl_down(suf[0], off), t1 = __shfl_down(suf[1], off);
+            if (lane + off < 64) {
+                suf[0] += t0;
+                suf[1] += t1;
+            }
+        }
+        if (lane == 0) {
+            wsum[par][wave][0] = suf[0];
+            wsum[par][wave][1] = suf[1];
+        }
+        __syncthreads();
+        uint32_t before[2] = {0u, 0u}, total[2] = {0u, 0u};
+        for (int k = 0; k < 4; ++k)
+            for (int q = 0; q < 2; ++q) {
+                if (k <= wave) before[q] += wsum[par][k][q];     // includes this wavefront: its suffix sum goes off below
+                total[q] += wsum[par][k][q];
+            }
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            const int sh = PERSONS_FIELD * (m % 3);
+            const uint32_t mask = (1u << PERSONS_FIELD) - 1u;
+            const int slot = base[m] + (int)(((before[m / 3] - suf[m / 3]) >> sh) & mask);
+            if (((flag[m / 3] >> sh) & 1u) && slot < max_persons) list[m][slot] = i;
+            base[m] += (int)((total[m / 3] >> sh) & mask);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int n = base[0];
+        int st = UP_PERSONS_OK;
+        if (n > max_persons) {
+            st = UP_PERSONS_OVERFLOW;
+        } else {
+            for (int idx = 0; idx < n && st == UP_PERSONS_OK; ++idx) {
+                if (idx >= base[1] || idx >= base[4]) {          // tl[idx], br[idx]
+                    st = UP_PERSONS_MISSING_CORNER;
+                    break;
+                }
+                const int tl = list[1][idx], br = list[4][idx];
+                const int r0 = tl / W, r1 = br / W;
+                if (r1 <= r0 || br - r1 * W <= tl - r0 * W) st = UP_PERSONS_EMPTY_BOX;
+                else if (idx >= base[2] || idx >= base[3]) st = UP_PERSONS_MISSING_CORNER;      // bl[idx], tr[idx]
+            }
+        }
+        count[b] = n;
+        status[b] = st;
+        s_n = n;
+        s_status = st;
+    }
+    __syncthreads();
+    if (s_status != UP_PERSONS_OK) return;
+    const int n = s_n, rows = njoints + 5;
+    int32_t* out = kpts + (size_t)b * max_persons * rows * 2;
+    for (int job = wave; job < n * njoints; job += 4) {
+        const int p = job / njoints, j = job - p * njoints;
+        const int tl = list[1][p], br = list[4][p];
+        const int r0 = tl / W, c0 = tl - r0 * W, r1 = br / W, c1 = br - r1 * W;
+        const int bw = c1 - c0;
+        const float* m = src + (joint_ch0 + j) * sj;
+        const int bi = box_first_max([&](int r, int c) -> float { return m[(r * W + c) * sp]; }, r0, c0, r1 - r0, bw, lane);
+        if (lane == 0) {
+            out[(p * rows + j) * 2] = c0 + bi % bw;
+            out[(p * rows + j) * 2 + 1] = r0 + bi / bw;
+        }
+    }
+    for (int t = tid; t < n * 5; t += 256) {
+        const int p = t / 5, m = t - p * 5;
+        const int pix = list[m][p], r = pix / W;
+        out[(p * rows + njoints + m) * 2] = pix - r * W;
+        out[(p * rows + njoints + m) * 2 + 1] = r;
     }
 }
 
@@ -1121,6 +1252,35 @@ extern "C" int up_box_argmax(const float* maps, int C, int H, int W, const int32
     hipLaunchKernelGGL(box_argmax_kernel, dim3(cdiv((long long)P * nch, 4)), dim3(256), 0, as_stream(stream), maps, H, W,
                        boxes, P, ch0, nch, out_hw);
     return check_launch("box_argmax");
+}
+extern "C" int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int C, int H, int W,
+                                 int box_ch0, int joint_ch0, int njoints, int max_persons, int32_t* count, int32_t* status,
+                                 int32_t* kpts, void* stream) {
+    UP_REQUIRE(maps && count && status && kpts, UP_ERR_INVALID, "persons_decode: null argument");
+    UP_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && stride_b > 0 && stride_j > 0 && stride_p > 0, UP_ERR_INVALID,
+               "persons_decode: %d samples of %d maps of %d x %d, strides %lld / %lld / %lld", B, C, H, W, (long long)stride_b,
+               (long long)stride_j, (long long)stride_p);
+    UP_REQUIRE(max_persons >= 1 && max_persons <= UP_PERSONS_CAP, UP_ERR_INVALID, "persons_decode: max_persons %d (1..%d)", max_persons,
+               UP_PERSONS_CAP);
+    UP_REQUIRE(box_ch0 >= 0 && (int64_t)box_ch0 + 5 <= C, UP_ERR_INVALID, "persons_decode: box channels %d..%lld of %d", box_ch0,
+               (long long)box_ch0 + 4, C);
+    UP_REQUIRE(joint_ch0 >= 0 && njoints >= 1 && (int64_t)joint_ch0 + njoints <= C, UP_ERR_INVALID,
+               "persons_decode: %d joint channels from %d of %d", njoints, joint_ch0, C);
+    const int64_t lim = INT32_MAX;
+    UP_REQUIRE((int64_t)H * W <= lim && stride_b <= lim && stride_j <= lim && stride_p <= lim && (B - 1) * stride_b <= lim &&
+                   (C - 1) * stride_j <= lim && ((int64_t)H * W - 1) * stride_p <= lim &&
+                   (B - 1) * stride_b + (C - 1) * stride_j + ((int64_t)H * W - 1) * stride_p <= lim &&
+                   (int64_t)B * max_persons * (njoints + 5) * 2 <= lim,
+               UP_ERR_INVALID, "persons_decode: %d samples of %d maps of %d x %d, %d persons: an index beyond the int32 range", B, C, H, W,
+               max_persons);
+    const dim3 grid(B), block(256);
+    if ((int64_t)5 * H * W <= DECODE_LDS)
+        hipLaunchKernelGGL(persons_kernel<true>, grid, block, 0, as_stream(stream), maps, stride_b, stride_j, stride_p, H, W,
+                           make_fastdiv(W), box_ch0, joint_ch0, njoints, max_persons, count, status, kpts);
+    else
+        hipLaunchKernelGGL(persons_kernel<false>, grid, block, 0, as_stream(stream), maps, stride_b, stride_j, stride_p, H, W,
+                           make_fastdiv(W), box_ch0, joint_ch0, njoints, max_persons, count, status, kpts);
+    return check_launch("persons_decode");
 }
 
 extern "C" int up_pck_accuracy(const float* pred_xy, const float* target_xy, int B, int J, int H, int W, int dataset,

@@ -1937,6 +1937,107 @@ def uniPose_kpts(maps: torch.Tensor, dataset: str, img_h: float = 368.0, img_w: 
     return kpts
 
 
+# status codes and the bound on max_persons of up_persons_decode (include/unipose_hip.h)
+PERSONS_OK, PERSONS_MISSING_CORNER, PERSONS_EMPTY_BOX, PERSONS_OVERFLOW = 0, 1, 2, 3
+PERSONS_CAP = 512
+
+
+def _persons_out(b, max_persons, rows, dev):
+    """(kpts, count, status) as views of ONE int32 buffer (also returned), so that the list form needs one copy to the host"""
+    nk = b * max_persons * rows * 2
+    buf = torch.empty(nk + 2 * b, dtype=torch.int32, device=dev)
+    return buf[:nk].view(b, max_persons, rows, 2), buf[nk:nk + b], buf[nk + b:], buf
+
+
+def _persons(t, strides, b, c, h, w, dataset, max_persons):
+    if dataset not in BOX_CHANNEL0:
+        raise ValueError(f"no box channels defined for dataset {dataset!r}")
+    f = BOX_CHANNEL0[dataset]
+    if c < f + 5:
+        raise IndexError(f"index {f + 4} is out of bounds for axis 0 with size {c}")
+    if not 1 <= max_persons <= PERSONS_CAP:
+        raise ValueError(f"max_persons {max_persons}: 1..{PERSONS_CAP}")
+    kpts, count, status, buf = _persons_out(b, max_persons, 19, t.device)
+    _C.check(_C.lib().up_persons_decode(t.data_ptr(), *strides, b, c, h, w, f, 1, 14, max_persons, count.data_ptr(), status.data_ptr(),
+                                        kpts.data_ptr(), _stream(t)), "persons_decode")
+    return kpts, count, status, buf
+
+
+def _persons_nchw(maps, dataset, max_persons):
+    _dev_ok(maps)
+    if maps.dtype != torch.float32:
+        raise TypeError(f"persons_decode: float32 maps, got {maps.dtype}")
+    m = _dense(maps.detach())
+    b, c, h, w = m.shape
+    return _persons(m, (c * h * w, h * w, 1), b, c, h, w, dataset, max_persons)
+
+
+def persons_decode(maps: torch.Tensor, dataset: str, max_persons: int = 16):
+    """The multi-person decode (``uniPose_kpts``) of every sample of NCHW float32 maps (B, C, h, w) in ONE launch, results left on
+    the device and no host synchronisation: (kpts (B, max_persons, 19, 2) int32 = (x, y), count (B,) int32, status (B,) int32).
+    count[b] is the number of centre peaks; status[b] is PERSONS_OK, PERSONS_MISSING_CORNER (where ``uniPose_kpts`` raises
+    IndexError), PERSONS_EMPTY_BOX (its ValueError) or PERSONS_OVERFLOW (count[b] > max_persons).  With PERSONS_OK the rows of
+    person p < count[b] are the 14 joints (channels 1..14, the reference's hard-wired ``box[1:15]``), then centre, top-left,
+    bottom-left, top-right, bottom-right; everything else in kpts is unspecified.  `dataset` picks the box channels
+    (BOX_CHANNEL0); max_persons is 1..PERSONS_CAP."""
+    return _persons_nchw(maps, dataset, max_persons)[:3]
+
+
+def persons_decode_nhwc(x: torch.Tensor, channels: int, dataset: str, max_persons: int = 16):
+    """``persons_decode`` of the first `channels` channels of an NHWC activation (B, h, w, ld) as a convolution leaves it (pad
+    channels are never read): no layout pass in between."""
+    _dev_ok(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"persons_decode_nhwc: float32 maps, got {x.dtype}")
+    b, h, w, _ = x.shape
+    ld = _nhwc_ok(x)
+    if not 0 < channels <= x.shape[3]:
+        raise ValueError(f"persons_decode_nhwc: {channels} channels of a tensor with {x.shape[3]}")
+    return _persons(x.detach(), (h * w * ld, 1, ld), b, channels, h, w, dataset, max_persons)[:3]
+
+
+def uniPose_kpts_batch(maps: torch.Tensor, dataset: str, max_persons: int = 16, strict: bool = True):
+    """``uniPose_kpts`` for every sample of a batch: a list with one entry per sample, each the reference's [[person, x, y], ...],
+    from one ``persons_decode`` launch and one copy to the host.  A sample with more than `max_persons` centre peaks makes the
+    call run once more with room for the largest count, so overflow never surfaces (beyond PERSONS_CAP such a sample goes through
+    ``uniPose_kpts``).  strict=True raises what the reference raises for the lowest failing sample (IndexError: a corner map with
+    fewer peaks than the centre map; ValueError: an empty box); strict=False puts None in that sample's place and keeps the rest."""
+    kpts, _, _, buf = _persons_nchw(maps, dataset, max_persons)
+    b = kpts.shape[0]
+
+    def fetch(k, flat):
+        host = flat.cpu().numpy()
+        nk = k.numel()
+        return host[:nk].reshape(k.shape), host[nk:nk + b], host[nk + b:]
+
+    kp, count, status = fetch(kpts, buf)
+    if (status == PERSONS_OVERFLOW).any():
+        kpts, _, _, buf = _persons_nchw(maps, dataset, min(int(count.max()), PERSONS_CAP))
+        kp, count, status = fetch(kpts, buf)
+    out = []
+    for i in range(b):
+        st, err = int(status[i]), None
+        if st == PERSONS_OVERFLOW:                 # more centre peaks than the kernel's lists hold: the per-sample path
+            try:
+                out.append(uniPose_kpts(maps[i:i + 1], dataset))
+                continue
+            except (IndexError, ValueError) as e:
+                err = e
+        elif st == PERSONS_MISSING_CORNER:
+            err = IndexError("list index out of range")
+        elif st == PERSONS_EMPTY_BOX:
+            err = ValueError("attempt to get argmax of an empty sequence")
+        if err is not None:
+            if strict:
+                raise err
+            out.append(None)
+            continue
+        n = int(count[i])
+        rows = kp[i, :n].reshape(-1, 2).tolist()
+        out.append([[r // kp.shape[2], x, y] for r, (x, y) in enumerate(rows)])
+    return out
+
+
 def get_kpts(maps: torch.Tensor, img_h: float = 368.0, img_w: float = 368.0):
     """utils/utils.py:94-106 on top of the device argmax: [[x, y], ...] for joints 1.. of sample 0."""
     _, _, idx = heatmap_argmax(maps[:1])

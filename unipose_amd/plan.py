@@ -1,5 +1,6 @@
 """``UniPosePlan`` — the image model's inference forward as ONE call into the C ABI (``up_unipose_forward``, ABI 9; at
-``stride != 8`` ``up_unipose_forward_upsampled``; key points instead of heat-maps: ``up_unipose_keypoints``).
+``stride != 8`` ``up_unipose_forward_upsampled``; key points instead of heat-maps: ``up_unipose_keypoints``; the persons of the
+box head: ``up_unipose_persons``).
 
 The reference's validation / test loops run ``heat = model(input)`` per batch (unipose.py:150-160).  A plan is built once
 from a model (any ``unipose`` with ``bbox`` or not, output stride 16 / 8): its BatchNorm layers are folded into the
@@ -11,6 +12,7 @@ and returns the heat-maps (the two slices of ``unipose(bbox=True)`` when the mod
     plan = UniPosePlan(model, batch=8, height=368, width=368)
     heat = plan(images)                      # equal bits to checkpoint.load_folded(...)(images)
     preds, maxvals, idx = plan.keypoints(images)     # equal bits to ops.heatmap_argmax(heat), without the NCHW heat-maps
+    kpts, count, status = plan.persons(images, "MPII")        # bbox=True models: ops.persons_decode of the maps, without them
 
 A model built with ``stride != 8`` (the reference's full-resolution mode, model/unipose.py:31-32) gives the heat-maps up-sampled
 to the input size, as the module does; ``keypoints`` then decodes on that grid without ever writing the up-sampled maps
@@ -149,6 +151,36 @@ class UniPosePlan:
         _C.check(_C.lib().up_unipose_keypoints(self._plan, x.data_ptr(), oh, ow, idx.data_ptr(), preds.data_ptr(), maxvals.data_ptr(),
                                                ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_keypoints")
         return preds, maxvals, idx
+
+    def persons(self, x: torch.Tensor, dataset: str, max_persons: int = 16, out=None):
+        """The multi-person decode of the forward's maps without writing them (``up_unipose_persons``): the device triple of
+        ``ops.persons_decode(torch.cat(plan(x), 1), dataset, max_persons)`` — (kpts (B, max_persons, 19, 2), count (B,),
+        status (B,)), all int32 — read straight from the NHWC output of the last convolution, on the maps' own grid (the one the
+        reference decodes on, also for a model with stride != 8).  `out`: a (kpts, count, status) triple to write into."""
+        from . import ops
+        if not self.bbox:
+            raise ValueError("UniPosePlan.persons: the model has no box head (unipose(..., bbox=True))")
+        if dataset not in ops.BOX_CHANNEL0:
+            raise ValueError(f"no box channels defined for dataset {dataset!r}")
+        f = ops.BOX_CHANNEL0[dataset]
+        if self.out_channels < f + 5:
+            raise IndexError(f"index {f + 4} is out of bounds for axis 0 with size {self.out_channels}")
+        if not 1 <= max_persons <= ops.PERSONS_CAP:
+            raise ValueError(f"max_persons {max_persons}: 1..{ops.PERSONS_CAP}")
+        x = self._input(x)
+        B = self.batch
+        shapes = ((B, max_persons, 19, 2), (B,), (B,))
+        if out is None:
+            out = ops._persons_out(B, max_persons, 19, self.device)[:3]
+        elif len(out) != 3:
+            raise ValueError("UniPosePlan.persons: `out` is a (kpts, count, status) triple")
+        kpts, count, status = (_check_out("UniPosePlan.persons", n, t, s, self.device, torch.int32)
+                               for n, t, s in zip(("kpts", "count", "status"), out, shapes))
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        _C.check(_C.lib().up_unipose_persons(self._plan, x.data_ptr(), f, 1, 14, max_persons, count.data_ptr(), status.data_ptr(),
+                                             kpts.data_ptr(), ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_persons")
+        return kpts, count, status
 
     def close(self):
         if self._plan:
