@@ -44,7 +44,12 @@ int up_abi_version(void);   /* 10; the revision that added the up_clip_* layout 
                                points kept it at 10: the additions are purely additive */
 
 /* Geometry of one 2-D convolution (nn.Conv2d as used at resnet.py:10-16,61,80-84,104-109;
- * wasp.py:9,52,59-60; decoder.py:17,22,26,30; model/uniposeLSTM.py:12-14,30-38,85-89). */
+ * wasp.py:9,52,59-60; decoder.py:17,22,26,30; model/uniposeLSTM.py:12-14,30-38,85-89).
+ * Any stride >= 1, dil >= 1, pad >= 0 and rectangular filters are accepted as long as P, Q follow from them and the
+ * output is not empty: a filter extent dil * (R - 1) + 1 (or the S one) larger than the padded input H + 2 * pad
+ * (W + 2 * pad) has no output pixel: every launching entry (up_pack_weights, up_conv2d_fwd*, up_conv2d_bwd_data*,
+ * up_conv2d_bwd_weight*) refuses it with UP_ERR_INVALID; the informational queries either do not validate the
+ * descriptor (up_conv_stats_tiles*) or answer 0 / UP_ERR_INVALID for it. */
 typedef struct {
     int32_t N, H, W;      /* input batch / height / width                                   */
     int32_t C, Cp;        /* real input channels, padded input channels (Cp%4==0, Cp>=C)    */

@@ -72,7 +72,8 @@ def conv_case(dev, n, c, h, w, k, r, stride, pad, dil, bias=False, relu=False, s
 
 def dgrad_add_case(dev, n, c, h, w, k, r, stride, pad, dil, seed=0, tol=2e-5):
     """up_conv2d_bwd_data with its optional addend: dx = conv_transpose(dy) + add (the skip-connection gradient)."""
-    wt = torch.randn(k, c, r, r, generator=g(seed)) * (2.0 / (c * r * r)) ** 0.5
+    r, s_ = (r, r) if isinstance(r, int) else r          # (R, S) for a rectangular filter
+    wt = torch.randn(k, c, r, s_, generator=g(seed)) * (2.0 / (c * r * s_)) ** 0.5
     x = torch.zeros(n, c, h, w, requires_grad=True)
     yr = F.conv2d(x, wt, stride=stride, padding=pad, dilation=dil)
     dy = torch.randn(yr.shape, generator=g(seed + 1))
@@ -158,44 +159,102 @@ def layout_case(dev):
     assert torch.equal(xd.grad.cpu(), dz)
 
 
-def maxpool_case(dev, n=2, c=8, h=9, w=10):
-    x = torch.randn(n, c, h, w, generator=g(3))
-    x[0, 0, :3, :3] = 1.5          # ties: first max in window-scan order must win
+def to_dev(x, dev, dtype=torch.float32, lanes=None):
+    """NCHW cpu tensor -> NHWC of `dtype` on dev, channels zero-padded to a multiple of 4 (fp32) or 8 (bf16; lanes=8: also an
+    fp32 tensor that a kernel turns into bf16)."""
+    return nhwc(x, dev, pad_to=(x.shape[1] + 7) // 8 * 8 if dtype == torch.bfloat16 or lanes == 8 else None).to(dtype)
+
+
+def same_values(a, b):
+    """== on every element, NaN at the same positions."""
+    return torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(0.0, float("inf"), -float("inf")),
+                                                             b.nan_to_num(0.0, float("inf"), -float("inf")))
+
+
+def maxpool_case(dev, n=2, c=8, h=9, w=10, in_dtype=torch.float32, out_dtype=None, x=None):
+    """in_dtype / out_dtype select the kernel instantiation (fp32 -> fp32, fp32 -> bf16 behind the stem, bf16 -> bf16); x: the input
+    (special values) instead of the random one.  The pool only selects, so values are compared with ==: against F.max_pool2d's,
+    rounded once to bf16 where the kernel stores bf16."""
+    out_dtype = out_dtype or in_dtype
+    bf = torch.bfloat16
+    if x is None:
+        x = torch.randn(n, c, h, w, generator=g(3))
+        x[0, 0, :3, :3] = 1.5          # ties: first max in window-scan order must win
+    if in_dtype == bf:
+        x = x.to(bf).float()
     xr = x.clone().requires_grad_(True)
     yr = F.max_pool2d(xr, 3, 2, 1)
     dy = torch.randn(yr.shape, generator=g(4))
+    if out_dtype == bf:
+        dy = dy.to(bf).float()
     yr.backward(dy)
-    xd = nhwc(x, dev).requires_grad_(True)
-    y = ops.MaxPool3s2.apply(xd)
-    y.backward(nhwc(dy, dev))
-    assert torch.equal(nchw(y, c), yr.detach())
-    assert rel(nchw(xd.grad, c), xr.grad) < 1e-6
+    xd = to_dev(x, dev, in_dtype, lanes=8 if out_dtype == bf else None).requires_grad_(True)
+    y = ops.MaxPool3s2.apply(xd) if out_dtype == in_dtype else ops.MaxPool3s2.apply(xd, out_dtype)
+    assert y.dtype == out_dtype and xd.dtype == in_dtype
+    y.backward(to_dev(dy, dev, out_dtype))
+    assert xd.grad.dtype == in_dtype
+    want = yr.detach().to(out_dtype).float()
+    assert same_values(nchw(y.float(), c), want), (nchw(y.float(), c) != want).nonzero()[:4]
+    gref = xr.grad.to(in_dtype).float()          # a bf16 gradient is the sum rounded once
+    assert rel(nchw(xd.grad.float(), c), gref) < 1e-6
 
 
-def bilinear_case(dev, n, c, h, w, p, q, tol=1e-5):
+def bf16_close(got, ref64, what=""):
+    """One bf16 rounding of the result (8 significant bits: up to 2^-8 of the value) on top of the fp32 tolerance of the same
+    operation: |got - ref64| <= 2^-8 |ref64| + 1e-5 max|ref64|, element by element."""
+    got, ref64 = got.double(), ref64.double()
+    bound = 2.0 ** -8 * ref64.abs() + 1e-5 * float(ref64.abs().max())
+    err = (got - ref64).abs()
+    assert bool((err <= bound).all()), (what, float((err / bound.clamp_min(1e-300)).max()))
+
+
+def bilinear_case(dev, n, c, h, w, p, q, tol=1e-5, dtype=torch.float32, f64=False):
+    """f64: float64 reference.  dtype bf16: inputs rounded to bf16 first, results within bf16_close of the float64 reference."""
+    bf = dtype == torch.bfloat16
+    rdt = torch.float64 if f64 or bf else torch.float32
     x = torch.randn(n, c, h, w, generator=g(5))
-    xr = x.clone().requires_grad_(True)
+    if bf:
+        x = x.to(dtype).float()
+    xr = x.to(rdt).clone().requires_grad_(True)
     yr = F.interpolate(xr, size=(p, q), mode="bilinear", align_corners=True)
     dy = torch.randn(yr.shape, generator=g(6))
-    yr.backward(dy)
-    xd = nhwc(x, dev).requires_grad_(True)
+    if bf:
+        dy = dy.to(dtype).float()
+    yr.backward(dy.to(rdt))
+    xd = to_dev(x, dev, dtype).requires_grad_(True)
     y = ops.Bilinear.apply(xd, p, q)
-    y.backward(nhwc(dy, dev))
-    assert rel(nchw(y, c), yr.detach()) < tol
-    assert rel(nchw(xd.grad, c), xr.grad) < tol
+    y.backward(to_dev(dy, dev, dtype))
+    assert y.dtype == dtype and xd.grad.dtype == dtype and y.shape[1:3] == (p, q)
+    if bf:
+        bf16_close(nchw(y.float(), c), yr.detach(), "y")
+        bf16_close(nchw(xd.grad.float(), c), xr.grad, "dx")
+    else:
+        assert rel(nchw(y, c), yr.detach()) < tol
+        assert rel(nchw(xd.grad, c), xr.grad) < tol
 
 
-def gap_case(dev, n=3, c=72, h=5, w=7):
+def gap_case(dev, n=3, c=72, h=5, w=7, dtype=torch.float32, f64=False):
+    bf = dtype == torch.bfloat16
+    rdt = torch.float64 if f64 or bf else torch.float32
     x = torch.randn(n, c, h, w, generator=g(7))
-    xr = x.clone().requires_grad_(True)
+    if bf:
+        x = x.to(dtype).float()
+    xr = x.to(rdt).clone().requires_grad_(True)
     yr = F.adaptive_avg_pool2d(xr, 1)
     dy = torch.randn(yr.shape, generator=g(8))
-    yr.backward(dy)
-    xd = nhwc(x, dev).requires_grad_(True)
+    if bf:
+        dy = dy.to(dtype).float()
+    yr.backward(dy.to(rdt))
+    xd = to_dev(x, dev, dtype).requires_grad_(True)
     y = ops.GlobalAvgPool.apply(xd)
-    y.backward(nhwc(dy, dev))
-    assert rel(nchw(y, c), yr.detach()) < 1e-5
-    assert rel(nchw(xd.grad, c), xr.grad) < 1e-6
+    y.backward(to_dev(dy, dev, dtype))
+    assert y.dtype == dtype and xd.grad.dtype == dtype
+    if bf:
+        bf16_close(nchw(y.float(), c), yr.detach(), "y")
+        bf16_close(nchw(xd.grad.float(), c), xr.grad, "dx")
+    else:
+        assert rel(nchw(y, c), yr.detach()) < 1e-5
+        assert rel(nchw(xd.grad, c), xr.grad) < 1e-6
 
 
 def concat_case(dev):
@@ -226,11 +285,12 @@ def dropout_case(dev):
     assert abs(float(y1.max()) - 1 / 0.7) < 1e-6
 
 
-def mse_case(dev):
-    y = torch.randn(2, 17, 9, 9, generator=g(14))
-    t = torch.rand(2, 17, 9, 9, generator=g(15))
-    yr = y.clone().requires_grad_(True)
-    lr = F.mse_loss(yr, t)
+def mse_case(dev, shape=(2, 17, 9, 9), f64=False):
+    rdt = torch.float64 if f64 else torch.float32
+    y = torch.randn(*shape, generator=g(14))
+    t = torch.rand(*shape, generator=g(15))
+    yr = y.to(rdt).clone().requires_grad_(True)
+    lr = F.mse_loss(yr, t.to(rdt))
     (lr * 3.0).backward()
     yd = y.to(dev).requires_grad_(True)
     l = ops.mse_loss(yd, t.to(dev))
@@ -239,9 +299,9 @@ def mse_case(dev):
     assert rel(yd.grad.cpu(), yr.grad) < 1e-6
 
 
-def avgpool_case(dev, h=40, w=48):
+def avgpool_case(dev, h=40, w=48, f64=False):
     c = torch.rand(2, 1, h, w, generator=g(16))
-    ref = F.avg_pool2d(c, 9, 8, 1)
+    ref = F.avg_pool2d(c.double() if f64 else c, 9, 8, 1)
     p, q = ref.shape[2:]
     buf = torch.zeros(2, p, q, 16).to(dev)
     ops.avgpool9s8_into(c.to(dev), buf, 14)
@@ -249,15 +309,19 @@ def avgpool_case(dev, h=40, w=48):
     assert float(buf[..., :14].abs().max()) == 0 and float(buf[..., 15].abs().max()) == 0
 
 
-def lstm_case(dev):
-    cg, n, h, w = 15, 2, 5, 6
-    G0 = torch.randn(n, h, w, 48, generator=g(17))
-    G = torch.randn(n, h, w, 60, generator=g(18))
-    cp = torch.randn(n, h, w, 16, generator=g(19))
-    dcell = torch.randn(n, h, w, 16, generator=g(20))
-    dhide = torch.randn(n, h, w, 16, generator=g(21))
+def lstm_case(dev, cg=15, scale=1.0, f64=False, fwd_tol=1e-5):
+    """cg: gate channels (pad lanes when not a multiple of 4); scale: factor on the gate pre-activations (40: every tanh / sigmoid
+    saturates, results must stay finite); f64: float64 reference; fwd_tol: forward tolerance (backward keeps 1e-5)."""
+    n, h, w = 2, 5, 6
+    co, rdt = ops.rup4(cg), torch.float64 if f64 else torch.float32
+    G0 = torch.randn(n, h, w, ops.rup4(3 * cg), generator=g(17)) * scale
+    G = torch.randn(n, h, w, 4 * cg, generator=g(18)) * scale
+    cp = torch.randn(n, h, w, co, generator=g(19))
+    dcell = torch.randn(n, h, w, co, generator=g(20))
+    dhide = torch.randn(n, h, w, co, generator=g(21))
+    finite = lambda *ts: all(bool(torch.isfinite(t_).all()) for t_ in ts)
     # reference math (model/uniposeLSTM.py:17-22, 41-62) with torch autograd
-    a = G0.clone().requires_grad_(True)
+    a = G0.to(rdt).clone().requires_grad_(True)
     gg, ii, oo = torch.tanh(a[..., :cg]), torch.sigmoid(a[..., cg:2 * cg]), torch.sigmoid(a[..., 2 * cg:3 * cg])
     cell = torch.tanh(gg * ii)
     hide = oo * cell
@@ -266,10 +330,11 @@ def lstm_case(dev):
     ad = G0.to(dev).requires_grad_(True)
     c_, h_ = ops.LSTM0Gates.apply(ad, cg)
     ((c_ * dcell.to(dev)).sum() + (h_ * dhide.to(dev)).sum()).backward()
-    assert rel(c_.detach().cpu()[..., :cg], cell.detach()) < 1e-5 and rel(h_.detach().cpu()[..., :cg], hide.detach()) < 1e-5
-    assert rel(ad.grad.cpu()[..., :45], a.grad[..., :45]) < 1e-5
-    b = G.clone().requires_grad_(True)
-    cpr = cp.clone().requires_grad_(True)
+    assert finite(c_.detach(), h_.detach(), ad.grad)
+    assert rel(c_.detach().cpu()[..., :cg], cell.detach()) < fwd_tol and rel(h_.detach().cpu()[..., :cg], hide.detach()) < fwd_tol
+    assert rel(ad.grad.cpu()[..., :3 * cg], a.grad[..., :3 * cg]) < 1e-5
+    b = G.to(rdt).clone().requires_grad_(True)
+    cpr = cp.to(rdt).clone().requires_grad_(True)
     gg, ii = torch.tanh(b[..., :cg]), torch.sigmoid(b[..., cg:2 * cg])
     oo, ff = torch.sigmoid(b[..., 2 * cg:3 * cg]), torch.sigmoid(b[..., 3 * cg:4 * cg])
     cell = ff * cpr[..., :cg] + ii * gg
@@ -279,7 +344,8 @@ def lstm_case(dev):
     cpd = cp.to(dev).requires_grad_(True)
     c_, h_ = ops.LSTMGates.apply(bd, cpd, cg)
     ((c_ * dcell.to(dev)).sum() + (h_ * dhide.to(dev)).sum()).backward()
-    assert rel(c_.detach().cpu()[..., :cg], cell.detach()) < 1e-5 and rel(h_.detach().cpu()[..., :cg], hide.detach()) < 1e-5
+    assert finite(c_.detach(), h_.detach(), bd.grad, cpd.grad)
+    assert rel(c_.detach().cpu()[..., :cg], cell.detach()) < fwd_tol and rel(h_.detach().cpu()[..., :cg], hide.detach()) < fwd_tol
     assert rel(bd.grad.cpu(), b.grad) < 1e-5
     assert rel(cpd.grad.cpu()[..., :cg], cpr.grad[..., :cg]) < 1e-5
 

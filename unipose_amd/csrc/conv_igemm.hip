@@ -1979,8 +1979,15 @@ static int check_desc(const up_conv_desc* d) {
                "conv desc: Cp=%d ldx=%d must be multiples of 4 with ldx >= Cp >= C=%d", d->Cp, d->ldx, d->C);
     UP_REQUIRE(d->ldy >= d->K, UP_ERR_INVALID, "conv desc: ldy=%d < K=%d", d->ldy, d->K);
     UP_REQUIRE(d->stride >= 1 && d->dil >= 1 && d->pad >= 0, UP_ERR_INVALID, "conv desc: bad stride/dil/pad");
-    int P = (d->H + 2 * d->pad - d->dil * (d->R - 1) - 1) / d->stride + 1;
-    int Q = (d->W + 2 * d->pad - d->dil * (d->S - 1) - 1) / d->stride + 1;
+    // a filter that does not fit the padded input even once has no output pixel: nothing to launch, and an empty tensor's
+    // null pointer must not be what refuses the call.  Tested on the extents, before the division: C rounds (-1) / 2 to 0,
+    // which would turn 5x5 on 4x4 at stride 2 into a 1x1 output.
+    const int eh = d->dil * (d->R - 1) + 1, ew = d->dil * (d->S - 1) + 1;
+    UP_REQUIRE(eh <= d->H + 2 * d->pad && ew <= d->W + 2 * d->pad, UP_ERR_INVALID,
+               "conv desc: empty output: filter extent %dx%d exceeds the padded input %dx%d", eh, ew, d->H + 2 * d->pad,
+               d->W + 2 * d->pad);
+    int P = (d->H + 2 * d->pad - eh) / d->stride + 1;
+    int Q = (d->W + 2 * d->pad - ew) / d->stride + 1;
     UP_REQUIRE(P == d->P && Q == d->Q, UP_ERR_INVALID, "conv desc: P,Q=(%d,%d) but geometry gives (%d,%d)", d->P,
                d->Q, P, Q);
     UP_REQUIRE((int64_t)d->N * d->H * d->W < (1ll << 31) && (int64_t)d->N * d->P * d->Q < (1ll << 31),

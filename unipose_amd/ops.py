@@ -105,6 +105,9 @@ def make_desc(x: torch.Tensor, weight: torch.Tensor, cfg: ConvCfg, ldy: Optional
         raise ValueError(f"input has {cp} physical channels, weight expects {c}")
     p = (h + 2 * cfg.pad - cfg.dil * (r - 1) - 1) // cfg.stride + 1
     q = (w + 2 * cfg.pad - cfg.dil * (s - 1) - 1) // cfg.stride + 1
+    if p <= 0 or q <= 0:
+        raise ValueError(f"convolution has an empty output: filter extent {cfg.dil * (r - 1) + 1}x{cfg.dil * (s - 1) + 1} "
+                         f"exceeds the padded input {h + 2 * cfg.pad}x{w + 2 * cfg.pad}")
     d = _C.ConvDesc()
     # Cp = physical channels of the input (pad channels are zeros and meet zero weights): lets a producer
     # pad e.g. the 304-channel decoder concat to 320 so that 32-wide K slices never straddle a filter tap
