@@ -409,7 +409,8 @@ int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, i
 int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q, void* stream);
 int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream);
 /* nn.Dropout (wasp.py:63, decoder.py:25,29): keep-mask from a counter hash of (seed, element index)
- * or, when ext_mask != NULL, from the caller (float 0/1) — the injectable-RNG hook used for parity. */
+ * or, when ext_mask != NULL, from the caller (float 0/1) — the injectable-RNG hook used for parity.
+ * UP_ERR_INVALID (nothing written): a null x / y / mask, n <= 0, p < 0 or p >= 1, an unknown dtype. */
 int up_dropout_fwd(const float* x, float* y, uint8_t* mask, const float* ext_mask, int64_t n,
                    float p, uint64_t seed, void* stream);
 int up_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float p, void* stream);
@@ -441,7 +442,9 @@ size_t up_mse_workspace(int64_t n);
 
 /* ---- ConvLSTM gate math (model/uniposeLSTM.py:16-24, 40-64).  `gates` is the fused gate
  * pre-activation tensor [rows][ldg] laid out g|i|o(|f), each Cg wide, produced by ONE convolution
- * over cat(x,h) with the gate weights stacked along K. ---- */
+ * over cat(x,h) with the gate weights stacked along K.  Row strides: gates and dgates [rows][ldg]; cprev [rows][ldc];
+ * cell, hide, dcell, dhide AND dcprev [rows][ldo] (dcprev is laid out like cell, not like cprev).  Only the lanes
+ * c < Cg of cell / hide / dcprev and c < 3 * Cg (4 * Cg) of dgates are written. ---- */
 int up_lstm0_fwd(const float* gates, int ldg, float* cell, float* hide, int ldo, int64_t rows, int Cg, void* stream);
 int up_lstm0_bwd(const float* gates, int ldg, const float* dcell, const float* dhide, int ldo,
                  float* dgates, int64_t rows, int Cg, void* stream);
@@ -491,7 +494,11 @@ int up_normalize_image(const float* img_hwc, int B, int H, int W, int C, float m
  * below 0.5 (acc), thr_pck * torso (pck) and thr_pckh * head (pckh); entry 0 of each is replaced by the mean over
  * the joints with any counted sample; visible[j] = 1 for those joints, *cnt = their number.  Head and torso sizes
  * come from the target joints of sample 0, as in the reference.  Arithmetic types follow the reference under
- * NumPy >= 2 (float32 thresholds, float64 distances). */
+ * NumPy >= 2 (float32 thresholds, float64 distances).  x is divided by H / 10 and y by W / 10, the reference's own order.
+ * Nothing is launched or written on UP_ERR_UNSUPPORTED (J outside 1..256: one workgroup, one thread per joint) and on
+ * UP_ERR_INVALID (a null pointer, B / H / W <= 0, an unknown dataset id, fewer joint channels than the dataset's head / torso
+ * formulas touch: LSP 15, COCO 14, Penn_Action 9, NTID 5, PoseTrack 14, BBC 8, MPII 11).  With no counted sample at all
+ * *cnt = 0, every result is 0 and entry 0 is not replaced. */
 enum { UP_DS_LSP = 0, UP_DS_COCO = 1, UP_DS_PENN_ACTION = 2, UP_DS_NTID = 3, UP_DS_POSETRACK = 4, UP_DS_BBC = 5,
        UP_DS_MPII = 6 };
 int up_pck_accuracy(const float* pred_xy, const float* target_xy, int B, int J, int H, int W, int dataset,

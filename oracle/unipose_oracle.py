@@ -360,18 +360,19 @@ def _head_and_torso(t0: np.ndarray, dataset: str):
     raise ValueError(f"unknown dataset {dataset!r}")
 
 
-def accuracy(output: np.ndarray, target: np.ndarray, thr_pck: float, thr_pckh: float, dataset: str):
+def accuracy(output: np.ndarray, target: np.ndarray, thr_pck: float, thr_pckh: float, dataset: str, swap_norm: bool = False):
     """utils/evaluate.py:58-172 `accuracy(..., hm_type='gaussian')` restated with masks instead of loops:
     joints from the argmax of both heat-map stacks; distance of prediction and target after dividing x by H/10 and
     y by W/10 (:68-70, the reference's own order); a joint counts for a sample when both target coordinates exceed
     1 (:12); per-joint fraction below 0.5 / thr_pckh*head / thr_pck*torso (:22-29); entry 0 of each result is
     replaced by the mean over the joints that had any valid sample (:75-90, :110-123, :155-170).
-    Returns (acc, PCK, PCKh, cnt, pred, visible) like the reference."""
+    Returns (acc, PCK, PCKh, cnt, pred, visible) like the reference.  swap_norm=True is NOT the reference: it divides x by
+    W/10 and y by H/10, so that the generator of the rectangular fixture (G18) can prove its inputs tell the two orders apart."""
     pred, _ = get_max_preds(output)
     tgt, _ = get_max_preds(target)
     b, j = pred.shape[:2]
     h, w = output.shape[2], output.shape[3]
-    norm = np.ones((b, 2)) * np.array([h, w]) / 10                      # float64, as in the reference
+    norm = np.ones((b, 2)) * np.array([w, h] if swap_norm else [h, w]) / 10                      # float64, as in the reference
     diff = pred.astype(np.float32) / norm[:, None, :] - tgt.astype(np.float32) / norm[:, None, :]
     dist = np.stack([[np.linalg.norm(diff[n, c]) for n in range(b)] for c in range(j)])      # (J, B) float64
     valid = ((tgt[:, :, 0] > 1) & (tgt[:, :, 1] > 1)).T                  # (J, B)

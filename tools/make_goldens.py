@@ -656,6 +656,72 @@ def g17_decode_full_res():
     save("g17_decode_full_res.npz", **res, sizes=np.array([368, 736, 368]))
 
 
+def g18_accuracy_rect():
+    """G18: the reference's `accuracy` (utils/evaluate.py, loaded by path like G7) for ALL SEVEN datasets on RECTANGULAR maps, 12 x 20
+    and 20 x 12, B = 3, J = each dataset's minimum and that + 3, both threshold pairs of G7.  Some targets at x <= 1, one target map
+    all zero.  The output background takes 16 values only, so that the file compresses (28 stacks of up to 52 KB).  The inputs must
+    discriminate: for every stack at least one of acc / PCK / PCKh changes when the normalisers H/10 and W/10 are exchanged (the
+    oracle with swap_norm=True), and no normalised distance lies within 1e-9 of a threshold it is compared with; the seed of a
+    stack is re-drawn until both hold."""
+    spec = importlib.util.spec_from_file_location("ref_evaluate", os.path.join(REF, "utils", "evaluate.py"))
+    ev = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ev)
+    need = dict(LSP=15, COCO=14, Penn_Action=9, NTID=5, PoseTrack=14, BBC=8, MPII=11)
+    thr = (("std", (0.2, 0.5)), ("tight", (0.03, 0.12)))
+    b = 3
+
+    def draw(rng, j, h, w):
+        tgt = np.zeros((b, j, h, w), np.float32)
+        outp = (rng.integers(-8, 8, (b, j, h, w)) / 64.0).astype(np.float32)
+        for n in range(b):
+            for c in range(j):
+                ty, tx = int(rng.integers(0, h)), int(rng.integers(0, w))
+                if rng.random() < 0.15:
+                    tx = int(rng.integers(0, 2))              # x <= 1: joint not counted
+                tgt[n, c, ty, tx] = 1.0
+                dy, dx = rng.integers(-4, 5, 2)               # prediction near (or far from) the target
+                py, px = int(np.clip(ty + dy, 0, h - 1)), int(np.clip(tx + dx, 0, w - 1))
+                outp[n, c, py, px] = 2.0 + rng.random()
+        tgt[1, 3] = 0.0                                       # an all-zero target map: argmax 0, masked to (0, 0)
+        return outp, tgt
+
+    def discriminates(ds, outp, tgt):
+        h, w = outp.shape[2:]
+        pred, t = O.get_max_preds(outp)[0], O.get_max_preds(tgt)[0]
+        dist = np.linalg.norm(pred / (np.array([h, w]) / 10) - t / (np.array([h, w]) / 10), axis=2)
+        valid = (t[:, :, 0] > 1) & (t[:, :, 1] > 1)
+        head, torso = O._head_and_torso(t[0], ds)
+        cuts = [0.5] + [tk * torso for _, (tk, _) in thr] + [th * head for _, (_, th) in thr]
+        if min(float(np.abs(dist[valid] - c).min()) for c in cuts) <= 1e-9:
+            return False
+        differs = False
+        for _, (tk, th) in thr:
+            a, s = O.accuracy(outp, tgt, tk, th, ds), O.accuracy(outp, tgt, tk, th, ds, swap_norm=True)
+            differs |= any(not np.array_equal(a[i], s[i]) for i in range(3))
+        return differs
+
+    res, seeds = {}, []
+    for ds in O.DATASETS:
+        for h, w in ((12, 20), (20, 12)):
+            for j in (need[ds], need[ds] + 3):
+                for seed in range(1000):          # (a distance of exactly 0.5 is one pixel along the 20-pixel side: common)
+                    outp, tgt = draw(np.random.default_rng([18, len(seeds), seed]), j, h, w)
+                    if discriminates(ds, outp, tgt):
+                        break
+                else:
+                    raise AssertionError("g18: no seed gives discriminating inputs")
+                seeds.append(seed)
+                k = f"{ds}_{h}x{w}_j{j}"
+                res.update({k + "_out": outp, k + "_tgt": tgt})
+                for tag, (tk, th) in thr:
+                    acc, pck, pckh, cnt, pred, vis = ev.accuracy(outp, tgt, tk, th, ds)
+                    res.update({f"{k}_{tag}_thr": np.array([tk, th]), f"{k}_{tag}_acc": acc, f"{k}_{tag}_pck": pck,
+                                f"{k}_{tag}_pckh": pckh, f"{k}_{tag}_cnt": np.array(cnt), f"{k}_{tag}_pred": pred, f"{k}_{tag}_vis": vis})
+    res["seeds"] = np.array(seeds)
+    print("g18: seeds", seeds)
+    save("g18_accuracy_rect.npz", **res)
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -669,9 +735,9 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
-               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res)
+               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect)
     for w in which:
         fns[w]()
