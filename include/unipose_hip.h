@@ -488,6 +488,32 @@ int up_make_gaussian_maps(const double* center_xy, int N, int H, int W, double s
 int up_normalize_image(const float* img_hwc, int B, int H, int W, int C, float mean, float stdv, float* out_chw,
                        void* stream);
 
+/* ---- training targets of the optional box head (ABI 10 addition; SURVEY 8f N2 + N4) ----
+ * The five maps the reference's loaders build with getBoundingBox (utils/lsp_lspet_data.py:71-113, returned as the sixth item of
+ * every sample, :247-249; the same function with a guard in utils/bbc_data.py:23-72), for a whole batch in one launch.
+ * kpt_xy (B,K,2) float64 pixel coordinates as for up_make_heatmaps; height, width: the image size the loader passes (img.shape);
+ * out (B,5,h,w) float32, dense, h = int(height / stride), w = int(width / stride); map order centre, top-left, bottom-left,
+ * top-right, bottom-right — the order up_persons_decode reads from box_ch0.  Per sample, statement by statement in float64 with
+ * int() truncating towards zero (negative values included), the reference's quirks kept:
+ *   a joint counts when kpt[1] >= 0 OR kpt[0] >= 0;  x collects kpt[1], y collects kpt[0] of the counted joints;
+ *   x_min = int(max(min(x), 0)), x_max = int(min(max(x), width)), y_min = int(max(min(y), 0)), y_max = int(min(max(y), height))
+ *     (x holds the second coordinate and is still bounded by `width`; x_max and y_max may be negative);
+ *   centre = ((x_min + x_max) / 2, (y_min + y_max) / 2);
+ *   cell(v, n) = int(min(int(v / stride), n / stride - 1)); the five pairs (cell(y, height), cell(x, width)) of the centre,
+ *     (y_min, x_min), (y_min, x_max), (y_max, x_min), (y_max, x_max) — n / stride - 1 is not rounded first (100 / 3 - 1 = 32.33);
+ *   map i is the Gaussian of up_make_heatmaps (float64 exp(-D2 / 2 / sigma^2), clipped to <= 1, < 0.0099 -> 0, stored float32)
+ *     centred at COLUMN = the first entry of pair i (from y) and ROW = the second (from x).  The reference hard-codes sigma 3.
+ * A sample without a counted joint gets the maps of bbc_data.py:32-36 (the box 0, 0, 0, 0: five Gaussians at pixel (0, 0)) and
+ * status[b] = UP_BOX_NO_VISIBLE_JOINT — where the LSP form raises ValueError (min of an empty list), which is the caller's
+ * business; every other sample gets UP_BOX_OK.  status (B) int32 may be NULL.  A sample never affects another.
+ * Contract: finite coordinates with |coordinate| <= 1e9 (non-finite values are outside it); any K >= 1.  One thread per output
+ * pixel walks the K joints of its sample.
+ * UP_ERR_INVALID (nothing launched): null kpt_xy / out, B, K, height or width <= 0, stride or sigma <= 0, h or w < 1,
+ * B * 5 * h * w beyond the int32 range. */
+enum { UP_BOX_OK = 0, UP_BOX_NO_VISIBLE_JOINT = 1 };
+int up_make_box_maps(const double* kpt_xy, int B, int K, int height, int width, double stride, double sigma, float* out,
+                     int32_t* status, void* stream);
+
 /* ---- PCK / PCKh evaluation (utils/evaluate.py:5-29 calc_dists / dist_acc, :58-172 accuracy) ----
  * From the joint coordinates of the predicted and the target heat-maps (two up_heatmap_argmax calls), entirely on
  * the device: per joint the fraction of counted samples (both target coordinates > 1) whose normalised distance is

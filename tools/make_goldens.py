@@ -722,6 +722,86 @@ def g18_accuracy_rect():
     save("g18_accuracy_rect.npz", **res)
 
 
+def g19_box_targets():
+    """G19: the training targets of the box head.  `guassian_kernel` and `getBoundingBox` are extracted with `ast` from
+    utils/lsp_lspet_data.py (the loader calls it at :222 and returns the maps as the sixth item of a sample) and from
+    utils/bbc_data.py (the same function with a guard for a sample without a counted joint), each pair executed in its own
+    namespace (the modules cannot be imported: cv2 is absent).  Key points go in as lists of lists like the loaders' annotations.
+    Per case `t`: t_kpt (K,2), t_cfg = (height, width, stride), t_lsp (5,h,w) float32 = the LSP form's (h,w,5) result moved to
+    channels first like Mytransforms.to_tensor does (:247), or an empty array with t_lsp_raises = 1 where it raised ValueError,
+    t_bbc the BBC form's."""
+    import ast
+
+    def extract(rel):
+        src = open(os.path.join(REF, *rel.split("/"))).read()
+        fns = [n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name in ("guassian_kernel", "getBoundingBox")]
+        assert sorted(f.name for f in fns) == ["getBoundingBox", "guassian_kernel"], rel
+        ns = {"np": np}
+        exec(compile(ast.Module(body=fns, type_ignores=[]), "reference:" + rel, "exec"), ns)
+        return ns["getBoundingBox"]
+
+    lsp, bbc = extract("utils/lsp_lspet_data.py"), extract("utils/bbc_data.py")
+    rng = np.random.default_rng(19)
+    cases = []
+
+    def add(tag, kpt, height, width, stride):
+        cases.append((tag, np.asarray(kpt, dtype=np.float64).reshape(-1, 2), height, width, stride))
+
+    def inside(k, height, width, margin=0.0):
+        return np.stack([rng.uniform(-margin, width + margin, k), rng.uniform(-margin, height + margin, k)], axis=1)
+
+    a = inside(14, 368, 368)
+    a[[3, 9]] = -1.0
+    add("a_two_invisible", a, 368, 368, 8)
+    b = np.stack([rng.uniform(5, 360, 6), rng.uniform(-60, -25, 6)], axis=1)     # every second coordinate negative ...
+    b[2, 1] = -20.6                                                              # ... the largest -20.6: x_max = int(-20.6) = -20
+    add("b_truncation", b, 368, 368, 8)
+    c = inside(14, 368, 368)
+    c[0], c[1], c[2] = (500.25, 499.5), (-30.5, 420.0), (367.9, 368.0)
+    add("c_beyond_368", c, 368, 368, 8)
+    c = inside(5, 100, 50)
+    c[0], c[1] = (130.2, 77.7), (49.99, 99.99)          # y_max = 100: int(100 / 3) = 33 > 100 / 3 - 1 = 32.33 -> 32
+    add("c_beyond_100x50_s3", c, 100, 50, 3)
+    d = inside(7, 96, 160)
+    d[4] = (40.5, 170.25)                                                        # second coordinate > width = 160
+    add("d_swapped_96x160", d, 96, 160, 8)
+    d = inside(7, 160, 96)
+    d[4] = (40.5, 150.75)                                                        # a row inside the image, but > width = 96
+    add("d_swapped_160x96", d, 160, 96, 8)
+    add("e_one_joint", [[201.5, 77.25]], 368, 368, 8)
+    add("f_none_counted", np.full((14, 2), -1.0), 368, 368, 8)
+    add("f_none_counted_k1", [[-3.0, -0.5]], 96, 160, 8)
+    add("g_2x5", inside(4, 16, 40, 6.0), 16, 40, 8)
+    add("g_1x1", inside(3, 8, 8, 4.0), 8, 8, 8)
+    h = inside(14, 368, 368)
+    h[0], h[1] = (183.99999999, 92.0), (12.0, 183.99999999)
+    add("h_below_integer", h, 368, 368, 8)
+    shapes = [(368, 368, 8), (96, 160, 8), (160, 96, 4), (100, 50, 3), (16, 40, 8), (64, 64, 8)]
+    for n in range(12):
+        height, width, stride = shapes[n % len(shapes)]
+        k = (1, 14, 65, 300)[n % 4]
+        kp = inside(k, height, width, 30.0)
+        kp[rng.uniform(size=k) < 0.15] = -1.0
+        add("i_random%02d_k%d" % (n, k), kp, height, width, stride)
+
+    out, raised = {}, []
+    for tag, kpt, height, width, stride in cases:
+        res_b = bbc(None, kpt.tolist(), height, width, stride)
+        try:
+            res_l = lsp(None, kpt.tolist(), height, width, stride).transpose(2, 0, 1)
+            assert np.array_equal(res_l, res_b.transpose(2, 0, 1)), tag      # the two forms differ only in the guard
+            flag = 0
+        except ValueError:
+            res_l, flag = np.zeros((0,), np.float32), 1
+            raised.append(tag)
+        assert res_b.dtype == np.float32 and res_b.shape == (int(height / stride), int(width / stride), 5)
+        out.update({tag + "_kpt": kpt, tag + "_cfg": np.array([height, width, stride], dtype=np.float64),
+                    tag + "_lsp": np.ascontiguousarray(res_l), tag + "_lsp_raises": np.array(flag, dtype=np.int32),
+                    tag + "_bbc": np.ascontiguousarray(res_b.transpose(2, 0, 1))})
+    print("g19:", len(cases), "cases; the LSP form raised ValueError for", raised)
+    save("g19_box_targets.npz", tags=np.array([c[0] for c in cases]), **out)
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -735,9 +815,10 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
-               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect)
+               g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect,
+               g19=g19_box_targets)
     for w in which:
         fns[w]()

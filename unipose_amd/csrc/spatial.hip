@@ -806,6 +806,51 @@ __global__ void __launch_bounds__(256) gaussian_map_kernel(const double* center,
     const int n = (int)(t / H);
     out[e] = target_gauss((double)x, (double)y, center[2 * n], center[2 * n + 1], sigma);
 }
+// Box-head targets (getBoundingBox, lsp_lspet_data.py:71-113 / bbc_data.py:23-72), every statement in float64 like Python's
+// floats; int() is trunc().  The reference calls the SECOND coordinate x and the first y, bounds x by `width` and y by `height`,
+// and then centres the Gaussian's column on the y-derived cell and its row on the x-derived one: kept as it is.
+__device__ __forceinline__ double box_cell(double v, double stride, double lim) {     // int(min(int(v / stride), lim))
+    const double q = trunc(v / stride);
+    return trunc(lim < q ? lim : q);
+}
+__global__ void __launch_bounds__(256) box_target_kernel(const double* kpt, int K, int height, int width, double stride,
+                                                         double sigma, int h, int w, float* out, int32_t* status,
+                                                         long long total /* B*h*w */) {
+    long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int x = (int)(e % w);
+    const long long t = e / w;
+    const int y = (int)(t % h);
+    const int b = (int)(t / h);
+    bool any = false;
+    double xlo = 0, xhi = 0, ylo = 0, yhi = 0;
+    for (int k = 0; k < K; ++k) {
+        const double k0 = kpt[((size_t)b * K + k) * 2], k1 = kpt[((size_t)b * K + k) * 2 + 1];
+        if (!(k1 >= 0.0 || k0 >= 0.0)) continue;                 // :76 — an OR: one coordinate >= 0 is enough
+        if (!any) { xlo = xhi = k1; ylo = yhi = k0; any = true; continue; }
+        xlo = k1 < xlo ? k1 : xlo;  xhi = k1 > xhi ? k1 : xhi;
+        ylo = k0 < ylo ? k0 : ylo;  yhi = k0 > yhi ? k0 : yhi;
+    }
+    double x_min = 0, x_max = 0, y_min = 0, y_max = 0;           // no counted joint: the zero box of bbc_data.py:32-36
+    if (any) {                                                   // :80-83
+        x_min = trunc(0.0 > xlo ? 0.0 : xlo);
+        x_max = trunc((double)width < xhi ? (double)width : xhi);
+        y_min = trunc(0.0 > ylo ? 0.0 : ylo);
+        y_max = trunc((double)height < yhi ? (double)height : yhi);
+    }
+    const double limh = (double)height / stride - 1.0, limw = (double)width / stride - 1.0;
+    // :97-101, then :106-108: the column is coord[i][0] (from y), the row coord[i][1] (from x)
+    const double col[3] = {box_cell((y_min + y_max) / 2.0, stride, limh), box_cell(y_min, stride, limh), box_cell(y_max, stride, limh)};
+    const double row[3] = {box_cell((x_min + x_max) / 2.0, stride, limw), box_cell(x_min, stride, limw), box_cell(x_max, stride, limw)};
+    const size_t hw = (size_t)h * w;
+    float* o = out + (size_t)b * 5 * hw + (size_t)y * w + x;
+    o[0] = target_gauss((double)x, (double)y, col[0], row[0], sigma);          // centre
+    o[hw] = target_gauss((double)x, (double)y, col[1], row[1], sigma);         // (y_min, x_min): top-left
+    o[2 * hw] = target_gauss((double)x, (double)y, col[1], row[2], sigma);     // (y_min, x_max): bottom-left
+    o[3 * hw] = target_gauss((double)x, (double)y, col[2], row[1], sigma);     // (y_max, x_min): top-right
+    o[4 * hw] = target_gauss((double)x, (double)y, col[2], row[2], sigma);     // (y_max, x_max): bottom-right
+    if (status && x == 0 && y == 0) status[b] = any ? UP_BOX_OK : UP_BOX_NO_VISIBLE_JOINT;
+}
 // (pixel - mean) / std, HWC -> CHW (Mytransforms.to_tensor + normalize, Mytransforms.py:10-41)
 __global__ void __launch_bounds__(256) normalize_image_kernel(const float* img, int C, int HW, float mean, float stdv,
                                                               float* out, long long total /* B*HW*C */) {
@@ -1227,6 +1272,22 @@ extern "C" int up_make_gaussian_maps(const double* center_xy, int N, int H, int 
     hipLaunchKernelGGL(gaussian_map_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), center_xy, H, W,
                        sigma, out, total);
     return check_launch("make_gaussian_maps");
+}
+extern "C" int up_make_box_maps(const double* kpt_xy, int B, int K, int height, int width, double stride, double sigma,
+                                float* out, int32_t* status, void* stream) {
+    UP_REQUIRE(kpt_xy && out, UP_ERR_INVALID, "make_box_maps: null argument");
+    UP_REQUIRE(B > 0 && K > 0 && height > 0 && width > 0 && stride > 0 && sigma > 0, UP_ERR_INVALID,
+               "make_box_maps: %d samples of %d joints, image %d x %d, stride %g, sigma %g", B, K, height, width, stride, sigma);
+    const double hd = trunc((double)height / stride), wd = trunc((double)width / stride);      // int(height / stride)
+    UP_REQUIRE(hd >= 1 && wd >= 1, UP_ERR_INVALID, "make_box_maps: image %d x %d at stride %g gives an empty map", height, width,
+               stride);
+    UP_REQUIRE((double)B * 5.0 * hd * wd <= (double)INT32_MAX, UP_ERR_INVALID,
+               "make_box_maps: %d samples of 5 maps of %.0f x %.0f: an index beyond the int32 range", B, hd, wd);
+    const int h = (int)hd, w = (int)wd;
+    long long total = (long long)B * h * w;
+    hipLaunchKernelGGL(box_target_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), kpt_xy, K, height, width,
+                       stride, sigma, h, w, out, status, total);
+    return check_launch("make_box_maps");
 }
 extern "C" int up_normalize_image(const float* img_hwc, int B, int H, int W, int C, float mean, float stdv,
                                   float* out_chw, void* stream) {

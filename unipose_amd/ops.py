@@ -1849,6 +1849,43 @@ def make_heatmaps(kpt_xy, height: int, width: int, stride: float, sigma: float, 
     return out
 
 
+BOX_OK, BOX_NO_VISIBLE_JOINT = 0, 1       # status codes of up_make_box_maps (include/unipose_hip.h)
+
+
+def make_box_maps(kpt_xy, height: int, width: int, stride: float, device, sigma: float = 3.0, empty: str = "raise"):
+    """Training targets of the box head on the device: the reference's ``getBoundingBox`` (lsp_lspet_data.py:71-113, the sixth
+    item of every loader sample; bbc_data.py:23-72) for a batch in one launch, quirks included (include/unipose_hip.h).  kpt_xy
+    (B,K,2) pixel coordinates (any array-like, kept in float64, or a device tensor); returns (B, 5, int(height/stride),
+    int(width/stride)) float32 = centre, top-left, bottom-left, top-right, bottom-right, the order ``persons_decode`` reads.
+    A sample without a counted joint (one with a coordinate >= 0): empty="raise" raises ValueError like the LSP loader's min()
+    of an empty list — decided from host annotations before anything is launched, from the kernel's status (one
+    synchronisation) when kpt_xy is already a device tensor; empty="bbc" gives the zero box of the BBC loader (five Gaussians
+    at pixel (0, 0)), never raises and never synchronises."""
+    if empty not in ("raise", "bbc"):
+        raise ValueError(f"make_box_maps: empty={empty!r} ('raise' or 'bbc')")
+    on_device = isinstance(kpt_xy, torch.Tensor) and kpt_xy.is_cuda
+
+    def refuse(counted):
+        bad = [i for i, c in enumerate(counted) if not c]
+        if bad:
+            raise ValueError(f"make_box_maps: sample {bad[0]} has no joint with a coordinate >= 0 "
+                             "(getBoundingBox takes min() of an empty list there)")
+
+    if empty == "raise" and not on_device:
+        host = torch.as_tensor(kpt_xy, dtype=torch.float64)
+        refuse(((host[..., 1] >= 0) | (host[..., 0] >= 0)).any(dim=-1).reshape(-1).tolist())
+    k = _as_f64(kpt_xy, device)
+    b, nk, _ = k.shape
+    h, w = int(height / stride), int(width / stride)
+    out = torch.empty((b, 5, max(h, 0), max(w, 0)), dtype=torch.float32, device=k.device)
+    status = torch.empty(b, dtype=torch.int32, device=k.device) if empty == "raise" and on_device else None
+    _C.check(_C.lib().up_make_box_maps(k.data_ptr(), b, nk, int(height), int(width), float(stride), float(sigma), out.data_ptr(),
+                                       status.data_ptr() if status is not None else None, _stream(out)), "make_box_maps")
+    if status is not None:
+        refuse((status.cpu() == BOX_OK).tolist())
+    return out
+
+
 def make_centermaps(center_xy, height: int, width: int, sigma: float = 3.0, device=None):
     """Gaussian centre maps (lsp_lspet_data.py:238-242): center_xy (N,2) -> (N, 1, height, width) float32."""
     c = _as_f64(center_xy, device)

@@ -149,10 +149,15 @@ class DeviceBatcher:
     * dict with ``pixels`` (…,H,W,3) uint8/float + ``kpts`` (…,K,2) + ``center`` (…,2): normalisation ``(x-128)/256``
       and the Gaussian targets (sigma, stride, 0.0099 cut, background = 1 - max; lsp_lspet_data.py:224-245) run as
       kernels where the loss reads them;
-    * the reference's tuple ``(input, heatmap, centermap, img_path)``: moved to the device unchanged."""
+    * the reference's tuple ``(input, heatmap, centermap, img_path)``: moved to the device unchanged.
 
-    def __init__(self, device, stride: float = 8, sigma: float = 3.0, center_sigma: float = 3.0):
+    ``bbox=True`` adds a fourth tensor, the five target maps of the box head: from ``kpts`` with ``ops.make_box_maps`` (the
+    loaders' ``getBoundingBox`` with its fixed sigma 3, lsp_lspet_data.py:71-113,222) for a dict, the sixth entry of the
+    reference's tuple ``(input, heatmap, centermap, img_path, 0, box)`` (lsp_lspet_data.py:249) otherwise."""
+
+    def __init__(self, device, stride: float = 8, sigma: float = 3.0, center_sigma: float = 3.0, bbox: bool = False):
         self.dev, self.stride, self.sigma, self.csigma = torch.device(device), stride, sigma, center_sigma
+        self.bbox = bool(bbox)
 
     def __call__(self, item):
         if isinstance(item, dict):
@@ -164,8 +169,16 @@ class DeviceBatcher:
             heat = ops.make_heatmaps(k.reshape((-1,) + k.shape[-2:]), h, w, self.stride, self.sigma, self.dev)
             c = np.asarray(item["center"], dtype=np.float64).reshape(-1, 2)
             cm = ops.make_centermaps(c, h, w, self.csigma, self.dev)
-            return (x.reshape(lead + x.shape[1:]), heat.reshape(lead + heat.shape[1:]), cm.reshape(lead + cm.shape[1:]))
+            out = (x.reshape(lead + x.shape[1:]), heat.reshape(lead + heat.shape[1:]), cm.reshape(lead + cm.shape[1:]))
+            if self.bbox:
+                box = ops.make_box_maps(k.reshape((-1,) + k.shape[-2:]), h, w, self.stride, self.dev)
+                out += (box.reshape(lead + box.shape[1:]),)
+            return out
         inp, heat, cm = item[0], item[1], item[2]
+        if self.bbox:
+            if len(item) < 6:
+                raise ValueError(f"bbox=True needs the loader's six-entry sample (the box maps last), got {len(item)} entries")
+            return inp.to(self.dev), heat.to(self.dev), cm.to(self.dev), item[5].to(self.dev)
         return inp.to(self.dev), heat.to(self.dev), cm.to(self.dev)
 
 
@@ -239,7 +252,13 @@ class _TrainerBase:
 
 
 class Trainer(_TrainerBase):
-    """Image model (reference ``unipose.py:37-231``)."""
+    """Image model (reference ``unipose.py:37-231``).
+
+    ``args.bbox`` (default off) trains the optional box head: the model is built with ``bbox=True`` and the batcher also
+    makes the five box target maps.  The reference has no training loop for this head (it keeps the head as comments), so
+    the loss is this project's decision: ``criterion(heat, heatmap) + criterion(box, boxmap)``, two ``MSELoss`` calls
+    summed the way the video driver sums its per-frame criterion calls (uniposeLSTM.py:118-133), one backward.  PCK / PCKh
+    and ``test`` read the joint maps only."""
     batch_size = 8
     sigma = 3
 
@@ -256,13 +275,22 @@ class Trainer(_TrainerBase):
             self.numClasses, self.batch_size, getattr(args, "train_batches", 4), size, seed=_rank_seed(1))
         self.val_loader = val_loader if val_loader is not None else SyntheticPoseData(
             self.numClasses, self.batch_size, getattr(args, "val_batches", 2), size, seed=2)
-        self.batcher = DeviceBatcher(dev, self.stride, self.sigma)
+        self.bbox = bool(getattr(args, "bbox", False))
+        self.batcher = DeviceBatcher(dev, self.stride, self.sigma, bbox=self.bbox)
         model = unipose(args.dataset, num_classes=self.numClasses, backbone="resnet", output_stride=16, sync_bn=True,
-                        freeze_bn=False, stride=self.stride)
+                        freeze_bn=False, stride=self.stride, bbox=self.bbox)
         self._setup(model, args, dev)
 
     def _load_pretrained(self, path):
         return checkpoint.load_checkpoint(self.model, path)            # unipose.py:78-90
+
+    def _forward_loss(self, batch):
+        """batch of the batcher -> (joint maps, loss); with the box head the loss is the sum of the two criterion calls"""
+        if not self.bbox:
+            heat = self.model(batch[0])
+            return heat, self.criterion(heat, batch[1])
+        heat, box = self.model(batch[0])
+        return heat, self.criterion(heat, batch[1]) + self.criterion(box, batch[3])
 
     def training(self, epoch):
         train_loss = 0.0
@@ -272,10 +300,9 @@ class Trainer(_TrainerBase):
         i = -1
         for i, item in enumerate(bar):
             self._lr_step()
-            input_var, heatmap_var, _ = self.batcher(item)
+            batch = self.batcher(item)
             self.optimizer.zero_grad()
-            heat = self.model(input_var)
-            loss = self.criterion(heat, heatmap_var)
+            _, loss = self._forward_loss(batch)
             train_loss += loss.item()
             loss.backward()
             self._optim_step()
@@ -291,9 +318,10 @@ class Trainer(_TrainerBase):
         metrics = PoseMetrics(self.numClasses)
         val_loss = 0.0
         for i, item in enumerate(_progress(self.val_loader, "val")):
-            input_var, heatmap_var, _ = self.batcher(item)
-            heat = self.model(input_var)
-            val_loss += self.criterion(heat, heatmap_var).item()
+            batch = self.batcher(item)
+            heatmap_var = batch[1]
+            heat, loss = self._forward_loss(batch)
+            val_loss += loss.item()
             acc, acc_PCK, acc_PCKh, _, _, visible = ops.accuracy(heat, heatmap_var, 0.2, 0.5, self.dataset)
             metrics.update(acc, acc_PCK, acc_PCKh, visible)
         self._after_validation(metrics)
@@ -306,6 +334,8 @@ class Trainer(_TrainerBase):
         self.model.eval()
         x = ops.normalize_image(pixels_hwc.to(self.device).float().unsqueeze(0))
         heat = self.model(x)
+        if self.bbox:
+            heat = heat[0]                 # the joint half
         h, w = x.shape[2], x.shape[3]
         up = ops.ToNCHW.apply(ops.Bilinear.apply(ops.ToNHWC.apply(heat), h, w), heat.shape[1])
         return ops.get_kpts(up, img_h=float(h), img_w=float(w)), up
