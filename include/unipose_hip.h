@@ -514,6 +514,33 @@ enum { UP_BOX_OK = 0, UP_BOX_NO_VISIBLE_JOINT = 1 };
 int up_make_box_maps(const double* kpt_xy, int B, int K, int height, int width, double stride, double sigma, float* out,
                      int32_t* status, void* stream);
 
+/* ---- augmentation of a training batch: one affine resample per image (ABI 10 addition) ----
+ * What the reference's loaders do to the pixels with Mytransforms.RandomResized, RandomRotate, RandomCrop / SinglePersonCrop and
+ * RandomHorizontalFlip (utils/Mytransforms.py, composed in utils/utils.py:231-345) followed by to_tensor + normalize, as ONE bilinear
+ * resample under a per-sample affine map (unipose_amd/augment.py composes the four steps; three OpenCV resamples in the reference).
+ * src_hwc (B,Hs,Ws,C) dense, src_type UP_PIX_U8 (uint8) or UP_PIX_F32 (float32), C = 1 .. 4;  out_chw (B,C,Ho,Wo) float32, dense.
+ * valid_hw (B,2) int32 on the device or NULL: the (height, width) of sample b that holds pixels, for images of different sizes
+ *   padded into one buffer; cut to 0 .. Hs / 0 .. Ws; NULL = Hs x Ws.  What lies beyond it is never read.
+ * inv (B / frames_per_map, 6) float64 on the device: image b uses map b / frames_per_map (the T frames of a clip share one), which
+ *   takes the OUTPUT pixel (column u, row v) to the source position  sx = i0*u + i1*v + i2,  sy = i3*u + i4*v + i5.
+ * Per output pixel, for every channel:
+ *   sx = fma(i0, u, fma(i1, v, i2)), sy likewise, in float64;  x0 = floor(sx), y0 = floor(sy);
+ *   fx = (float)(sx - x0), fy = (float)(sy - y0)  (the float64 difference rounded once);
+ *   the taps (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1): a tap with 0 <= x < valid width and 0 <= y < valid height is the
+ *     pixel converted to float32, any other tap is `border` and is not loaded — a constant border that blends, as
+ *     cv2.warpAffine(borderValue=...) does.  Unless -1 <= x0 <= width-1 and -1 <= y0 <= height-1, decided in float64 (so also for
+ *     NaN, infinities and coordinates such as 1e12 that no integer holds), all four taps are border;
+ *   in float32, each line one rounding:  top = fmaf(fx, v01 - v00, v00);  bot = fmaf(fx, v11 - v10, v10);
+ *     val = fmaf(fy, bot - top, top);  out = (val - mean) / stdv  — the float32 division of up_normalize_image, so an identity map
+ *     (and any integer translation or mirror: fx = fy = 0) reproduces up_normalize_image bit for bit.
+ * The reference uses border = mean = 128, stdv = 256.  One thread per output pixel covers the C channels; consecutive threads
+ * store consecutive u; 64-bit indexing; no LDS; a grid of at most 2^21 threads walks larger outputs in further trips.
+ * UP_ERR_INVALID (nothing launched): null src_hwc / inv / out_chw, an unknown src_type, B, Hs, Ws, Ho or Wo <= 0, C outside 1 .. 4,
+ * frames_per_map < 1 or not a divisor of B, stdv <= 0 (or NaN). */
+enum { UP_PIX_U8 = 0, UP_PIX_F32 = 1 };
+int up_augment_image(const void* src_hwc, int src_type, int B, int Hs, int Ws, int C, const int32_t* valid_hw, const double* inv,
+                     int frames_per_map, float border, float mean, float stdv, float* out_chw, int Ho, int Wo, void* stream);
+
 /* ---- PCK / PCKh evaluation (utils/evaluate.py:5-29 calc_dists / dist_acc, :58-172 accuracy) ----
  * From the joint coordinates of the predicted and the target heat-maps (two up_heatmap_argmax calls), entirely on
  * the device: per joint the fraction of counted samples (both target coordinates > 1) whose normalised distance is

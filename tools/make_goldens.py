@@ -802,6 +802,113 @@ def g19_box_targets():
     save("g19_box_targets.npz", tags=np.array([c[0] for c in cases]), **out)
 
 
+def g20_augment():
+    """G20: augmentation.  The genuine utils/Mytransforms.py is loaded by file path with tools/cv2_standin.py (this project's
+    shape-only stand-in: getRotationMatrix2D by OpenCV's documented formula, resize / warpAffine / copyMakeBorder returning zero
+    arrays of the documented size) in sys.modules as `cv2`.  Recorded, for explicit parameters (no seeds):
+      points   p<n>_*: kpt0 (K,3) = x, y, visible and center0 going through the genuine resize -> rotate -> RandomCrop.get_params
+               (random.uniform of the loaded module scripted) -> crop -> hflip / hflip_BBC / no flip; p<n>_cfg = (h, w, ratio,
+               degree, ratio_x, ratio_y, size, flip kind 0 none / 1 hflip / 2 hflip_BBC / 3 hflip_NTID); results after rotate (k_rot, c_rot), the
+               crop offsets (off) and at the end (k_out, c_out).  Where flip kind is 0 or 1 the same parameters also go through the
+               genuine Compose([RandomResized(), RandomRotate(40), RandomCrop(size), RandomHorizontalFlip(prob)]) and must agree.
+      pixels   i<n>_*: the image side of the genuine crop and hflip (pure numpy) and normalize(to_tensor(.)) on small uint8
+               images: src (H,W,3), cfg = (offset_left, offset_up, size, flip), out (3,size,size) float32.
+    Nothing the reference's image RESAMPLING produces can be recorded: OpenCV is absent."""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import cv2_standin
+    sys.modules["cv2"] = cv2_standin
+    import collections
+    import collections.abc
+    if not hasattr(collections, "Iterable"):
+        collections.Iterable = collections.abc.Iterable          # Mytransforms.py:60 (removed from `collections` in Python 3.10)
+    spec = importlib.util.spec_from_file_location("ref_mytransforms", os.path.join(REF, "utils", "Mytransforms.py"))
+    T = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(T)
+    real_random = T.random
+
+    def scripted(values, flip_draw=0.0):
+        vals = list(values)
+        return types.SimpleNamespace(uniform=lambda a, b: vals.pop(0), random=lambda: flip_draw)
+
+    rng = np.random.default_rng(20)
+    out, tags = {}, []
+
+    def points(h, w, ratio, degree, rx, ry, size, kind, k, invisible=()):
+        tag = "p%02d" % len([t for t in tags if t[0] == "p"])
+        kpt0 = np.concatenate([np.stack([rng.uniform(0, w - 1, k), rng.uniform(0, h - 1, k)], axis=1), np.ones((k, 1))], axis=1)
+        for j in invisible:
+            kpt0[j] = (-1.0, -1.0, 0.0)
+        center0 = np.array([w / 2 + rng.uniform(-8, 8), h / 2 + rng.uniform(-8, 8)])
+        img = np.zeros((h, w, 3), dtype=np.uint8)
+        kpt, center = [list(r) for r in kpt0.tolist()], center0.tolist()
+        img, kpt, center = T.resize(img, kpt, center, ratio)
+        img, kpt, center = T.rotate(img, kpt, center, degree)
+        k_rot, c_rot, canvas = np.array(kpt), np.array(center), img.shape[:2]
+        T.random = scripted([rx, ry])
+        try:
+            left, up = T.RandomCrop.get_params(img, center, (size, size), 5)
+        finally:
+            T.random = real_random
+        img, kpt, center = T.crop(img, kpt, center, left, up, size, size)
+        if kind == 1:
+            img, kpt, center = T.hflip(img, kpt, center)
+        elif kind == 2:
+            img, kpt, center = T.hflip_BBC(img, kpt, center)
+        elif kind == 3:
+            img, kpt, center = T.hflip_NTID(img, kpt, center)
+        assert img.shape == (size, size, 3)
+        if kind in (0, 1):                                       # the genuine composition draws and does the same
+            T.random = scripted([ratio, degree, rx, ry], flip_draw=0.0)
+            try:
+                comp = T.Compose([T.RandomResized(), T.RandomRotate(40), T.RandomCrop(size), T.RandomHorizontalFlip(float(kind))])
+                _, kc, cc = comp(np.zeros((h, w, 3), dtype=np.uint8), [list(r) for r in kpt0.tolist()], center0.tolist(), 1.0)
+            finally:
+                T.random = real_random
+            assert np.array_equal(np.array(kc), np.array(kpt)) and np.array_equal(np.array(cc), np.array(center)), tag
+        out.update({tag + "_cfg": np.array([h, w, ratio, degree, rx, ry, size, kind], dtype=np.float64), tag + "_kpt0": kpt0,
+                    tag + "_center0": center0, tag + "_k_rot": k_rot, tag + "_c_rot": c_rot,
+                    tag + "_canvas": np.array(canvas, dtype=np.int64), tag + "_off": np.array([left, up], dtype=np.int64),
+                    tag + "_k_out": np.array(kpt), tag + "_c_out": np.array(center)})
+        tags.append(tag)
+
+    sources = [(368, 368), (300, 400), (480, 270), (120, 50), (97, 63), (64, 64)]          # two narrower than 64
+    n = 0
+    for ratio in (0.3, 0.55, 1.0, 1.1):
+        for degree in (0.0, 37.0, -40.0, 90.0, 12.5):
+            h, w = sources[n % len(sources)]
+            kind = (0, 1, 2)[n % 3]
+            k = 7 if kind == 2 else 14
+            inv = () if n % 4 == 0 else ((2, 11) if k == 14 else (1, 6))
+            points(h, w, ratio, degree, float(rng.uniform(0, 1)), float(rng.uniform(0, 1)), (368, 96, 46)[n % 3], kind, k, inv)
+            n += 1
+    points(368, 368, 0.8, 180.0, 0.0, 1.0, 368, 1, 14, (0, 5))          # extreme perturbation draws: int(-5.0), int(5.0)
+    points(200, 40, 2.05, -17.0, 0.999, 0.001, 128, 2, 7)               # int(4.99) = 4, int(-4.99) = -4; ratio above 1
+    points(368, 368, 1.0, 0.0, 0.5, 0.5, 368, 0, 14, (13,))             # nothing but the crop
+
+    def pixels(h, w, left, up, size, flip):
+        tag = "i%02d" % len([t for t in tags if t[0] == "i"])
+        src = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        img, _, _ = T.crop(src, [], [0.0, 0.0], left, up, size, size)
+        if flip:
+            img, _, _ = T.hflip(img, [[0.0, 0.0, 1.0] for _ in range(12)], [0.0, 0.0])
+        res = T.normalize(T.to_tensor(img), [128.0, 128.0, 128.0], [256.0, 256.0, 256.0]).numpy()
+        assert res.dtype == np.float32 and res.shape == (3, size, size)
+        out.update({tag + "_src": src, tag + "_cfg": np.array([left, up, size, int(flip)], dtype=np.int64), tag + "_out": res})
+        tags.append(tag)
+
+    for h, w in ((20, 12), (12, 20)):
+        pixels(h, w, -3, -2, 16, False)          # negative offsets: a border at the left and on top
+        pixels(h, w, 2, 3, 16, True)             # runs past the far edges
+        pixels(h, w, -1, 6, 16, True)
+        pixels(h, w, 0, 0, 16, False)
+    pixels(16, 16, 0, 0, 16, True)               # the mirror alone
+    pixels(5, 7, -9, 3, 16, False)               # a source smaller than the crop in both directions, in its top right corner
+    points(300, 400, 0.7, 21.0, 0.3, 0.8, 96, 3, 18, (4, 17))            # hflip_NTID (18 joints); drawn last: the cases above keep their values
+    print("g20:", len(tags), "cases")
+    save("g20_augment.npz", tags=np.array(tags), **out)
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -815,10 +922,10 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
                g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect,
-               g19=g19_box_targets)
+               g19=g19_box_targets, g20=g20_augment)
     for w in which:
         fns[w]()

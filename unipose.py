@@ -24,6 +24,8 @@ def parse_args(argv=None):
     p.add_argument("--train_batches", default=4, type=int, help="synthetic batches per epoch")
     p.add_argument("--val_batches", default=2, type=int)
     p.add_argument("--bbox", action="store_true", help="train the optional box head too (model/unipose.py:34-35; default off)")
+    p.add_argument("--augment", action="store_true",
+                   help="augment the training batches on the device (resize, rotate, crop, mirror as utils/Mytransforms.py; default off)")
     return p.parse_args(argv)
 
 

@@ -21,6 +21,8 @@ def parse_args(argv=None):
     p.add_argument("--size", default=368, type=int)
     p.add_argument("--train_batches", default=2, type=int)
     p.add_argument("--val_batches", default=1, type=int)
+    p.add_argument("--augment", action="store_true",
+                   help="augment the training batches on the device (resize, rotate, crop, mirror as utils/Mytransforms.py; default off)")
     args = p.parse_args(argv)
     args.dataset = "Penn_Action"
     return args

@@ -147,6 +147,7 @@ SIGNATURES = {
     "up_make_box_maps": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p]),
     "up_make_gaussian_maps": (_i, [_p, _i, _i, _i, C.c_double, _p, _p]),
     "up_normalize_image": (_i, [_p, _i, _i, _i, _i, _f, _f, _p, _p]),
+    "up_augment_image": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _f, _f, _f, _p, _i, _i, _p]),
     "up_pck_accuracy": (_i, [_p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     "up_peak_mask": (_i, [_p, _i, _i, _i, _p, _p]),
     "up_box_argmax": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),

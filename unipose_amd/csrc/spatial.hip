@@ -862,6 +862,61 @@ __global__ void __launch_bounds__(256) normalize_image_kernel(const float* img, 
     const long long b = t / HW;
     out[((size_t)b * C + c) * HW + p] = (img[e] - mean) / stdv;
 }
+// Augmentation as ONE resample (RandomResized + RandomRotate + RandomCrop + RandomHorizontalFlip of utils/Mytransforms.py composed
+// into one affine map by unipose_amd/augment.py), fused with to_tensor + normalize: one thread per output pixel, all C channels;
+// the semantics, operation by operation, are in include/unipose_hip.h.  Coordinates in float64, the blend in float32 with fused
+// multiply-adds written out (fma / fmaf, the same single rounding on the device and in the host build); a tap outside the sample's
+// valid extent is the border constant and is not loaded.  Store-bound: the four taps of neighbouring threads share cache lines.
+__device__ __forceinline__ float aug_px(const float* p) { return *p; }
+__device__ __forceinline__ float aug_px(const uint8_t* p) { return (float)*p; }
+template <typename T>
+__global__ void __launch_bounds__(256) augment_image_kernel(const T* src, int Hs, int Ws, int C, const int32_t* valid_hw,
+                                                            const double* inv, int frames_per_map, float border, float mean,
+                                                            float stdv, float* out, int Ho, int Wo,
+                                                            long long total /* B*Ho*Wo */) {
+    UP_GRID_STRIDE(e, total) {
+        const int u = (int)(e % Wo);
+        const int64_t t = e / Wo;
+        const int v = (int)(t % Ho);
+        const int64_t b = t / Ho;
+        const double* m = inv + (b / frames_per_map) * 6;
+        int Hv = Hs, Wv = Ws;
+        if (valid_hw) {                                  // device data: cut to the buffer, never trusted beyond it
+            Hv = min(max(valid_hw[2 * b], 0), Hs);
+            Wv = min(max(valid_hw[2 * b + 1], 0), Ws);
+        }
+        const double sx = fma(m[0], (double)u, fma(m[1], (double)v, m[2]));
+        const double sy = fma(m[3], (double)u, fma(m[4], (double)v, m[5]));
+        const double x0d = floor(sx), y0d = floor(sy);
+        // decided in float64 (false for NaN and for anything too large to index): otherwise all four taps are border
+        const bool near = x0d >= -1.0 && x0d <= (double)(Wv - 1) && y0d >= -1.0 && y0d <= (double)(Hv - 1);
+        float val[4] = {border, border, border, border};
+        if (near) {
+            const int x0 = (int)x0d, y0 = (int)y0d;      // -1 .. Wv-1, -1 .. Hv-1
+            const float fx = (float)(sx - x0d), fy = (float)(sy - y0d);
+            const bool xa = x0 >= 0, xb = x0 + 1 < Wv, ya = y0 >= 0, yb = y0 + 1 < Hv;
+            const int64_t p = ((b * Hs + y0) * Ws + x0) * C;          // may lie before the sample: read at valid taps only
+            const int64_t row = (int64_t)Ws * C;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c < C) {
+                    const float v00 = ya && xa ? aug_px(src + p + c) : border;
+                    const float v01 = ya && xb ? aug_px(src + p + C + c) : border;
+                    const float v10 = yb && xa ? aug_px(src + p + row + c) : border;
+                    const float v11 = yb && xb ? aug_px(src + p + row + C + c) : border;
+                    const float top = fmaf(fx, v01 - v00, v00);
+                    const float bot = fmaf(fx, v11 - v10, v10);
+                    val[c] = fmaf(fy, bot - top, top);
+                }
+            }
+        }
+        const int64_t hw = (int64_t)Ho * Wo;
+        float* o = out + b * C * hw + (int64_t)v * Wo + u;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < C) o[c * hw] = (val[c] - mean) / stdv;
+    }
+}
 
 // ---- PCK / PCKh accuracy on joint coordinates (utils/evaluate.py:5-29,58-172) -------------------------------------
 // One workgroup; thread j owns joint j.  Arithmetic types follow the reference under NumPy >= 2: coordinates float32,
@@ -1297,6 +1352,28 @@ extern "C" int up_normalize_image(const float* img_hwc, int B, int H, int W, int
     hipLaunchKernelGGL(normalize_image_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), img_hwc, C,
                        H * W, mean, stdv, out_chw, total);
     return check_launch("normalize_image");
+}
+extern "C" int up_augment_image(const void* src_hwc, int src_type, int B, int Hs, int Ws, int C, const int32_t* valid_hw,
+                                const double* inv, int frames_per_map, float border, float mean, float stdv, float* out_chw,
+                                int Ho, int Wo, void* stream) {
+    UP_REQUIRE(src_hwc && inv && out_chw, UP_ERR_INVALID, "augment_image: null argument");
+    UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "augment_image: source type %d", src_type);
+    UP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, UP_ERR_INVALID,
+               "augment_image: %d images of %d x %d to %d x %d", B, Hs, Ws, Ho, Wo);
+    UP_REQUIRE(C >= 1 && C <= 4, UP_ERR_INVALID, "augment_image: %d channels (1 .. 4)", C);
+    UP_REQUIRE(frames_per_map >= 1 && B % frames_per_map == 0, UP_ERR_INVALID,
+               "augment_image: %d frames per map do not divide %d images", frames_per_map, B);
+    UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "augment_image: std %g", (double)stdv);
+    const long long total = (long long)B * Ho * Wo;
+    if (src_type == UP_PIX_U8)
+        hipLaunchKernelGGL(augment_image_kernel<uint8_t>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
+                           (const uint8_t*)src_hwc, Hs, Ws, C, valid_hw, inv, frames_per_map, border, mean, stdv, out_chw, Ho, Wo,
+                           total);
+    else
+        hipLaunchKernelGGL(augment_image_kernel<float>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
+                           (const float*)src_hwc, Hs, Ws, C, valid_hw, inv, frames_per_map, border, mean, stdv, out_chw, Ho, Wo,
+                           total);
+    return check_launch("augment_image");
 }
 
 extern "C" int up_peak_mask(const float* maps, int nmaps, int H, int W, uint8_t* mask, void* stream) {

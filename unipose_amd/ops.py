@@ -1907,6 +1907,44 @@ def normalize_image(img_hwc: torch.Tensor, mean: float = 128.0, std: float = 256
     return out
 
 
+def augment_image(pixels: torch.Tensor, inv, out_hw, border: float = 128.0, mean: float = 128.0, std: float = 256.0,
+                  valid_hw=None, frames_per_map: int = 1):
+    """Augmentation + to_tensor + normalize of a batch in one launch (``up_augment_image``, include/unipose_hip.h): pixels
+    (N,H,W,C) uint8 or float32 on the device, C = 1 .. 4; inv (N / frames_per_map, 2, 3), any array-like, kept in float64: the
+    affine map from an OUTPUT pixel (u, v, 1) to its source position (``augment.compose`` makes it); out_hw = (Ho, Wo).  Every
+    output pixel is a bilinear sample of its own image, taps outside the image (or outside valid_hw (N,2) = (height, width) per
+    sample, for images padded into one buffer) are ``border``; returns (N,C,Ho,Wo) float32 ``(value - mean) / std``.
+    Non-finite entries of a map given on the host are refused here, before anything is launched.  A map that already lives on
+    the device is passed through unchecked (checking it would synchronise): the kernel decides in float64, so a NaN, an infinity
+    or a coordinate too large to index makes all four taps border and nothing is read."""
+    _dev_ok(pixels)
+    if pixels.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"augment_image: uint8 or float32 pixels, got {pixels.dtype}")
+    if pixels.dim() != 4:
+        raise ValueError(f"augment_image: pixels (N,H,W,C), got {tuple(pixels.shape)}")
+    x = pixels if pixels.is_contiguous() else pixels.contiguous()
+    n, h, w, c = x.shape
+    m = torch.as_tensor(inv, dtype=torch.float64) if not (isinstance(inv, torch.Tensor) and inv.is_cuda) else None
+    if m is not None and not bool(torch.isfinite(m).all()):
+        raise ValueError("augment_image: a map with a non-finite entry")
+    m = _as_f64(inv if m is None else m, x.device)
+    fpm = int(frames_per_map)
+    if fpm < 1 or n % fpm or tuple(m.shape) != (n // fpm, 2, 3):
+        raise ValueError(f"augment_image: maps {tuple(m.shape)} for {n} images with {frames_per_map} frames per map "
+                         "((N / frames_per_map, 2, 3) expected)")
+    valid = None
+    if valid_hw is not None:
+        valid = torch.as_tensor(valid_hw).to(device=x.device, dtype=torch.int32).contiguous()
+        if tuple(valid.shape) != (n, 2):
+            raise ValueError(f"augment_image: valid_hw {tuple(valid.shape)} for {n} images ((N, 2) expected)")
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((n, c, max(ho, 0), max(wo, 0)), dtype=torch.float32, device=x.device)
+    _C.check(_C.lib().up_augment_image(x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, n, h, w, c, _ptr(valid), m.data_ptr(), fpm,
+                                       float(border), float(mean), float(std), out.data_ptr(), ho, wo, _stream(x)),
+             "augment_image")
+    return out
+
+
 DATASET_IDS = {"LSP": 0, "COCO": 1, "Penn_Action": 2, "NTID": 3, "PoseTrack": 4, "BBC": 5, "MPII": 6}
 
 

@@ -153,33 +153,66 @@ class DeviceBatcher:
 
     ``bbox=True`` adds a fourth tensor, the five target maps of the box head: from ``kpts`` with ``ops.make_box_maps`` (the
     loaders' ``getBoundingBox`` with its fixed sigma 3, lsp_lspet_data.py:71-113,222) for a dict, the sixth entry of the
-    reference's tuple ``(input, heatmap, centermap, img_path, 0, box)`` (lsp_lspet_data.py:249) otherwise."""
+    reference's tuple ``(input, heatmap, centermap, img_path, 0, box)`` (lsp_lspet_data.py:249) otherwise.
 
-    def __init__(self, device, stride: float = 8, sigma: float = 3.0, center_sigma: float = 3.0, bbox: bool = False):
+    ``augment=`` an ``augment.Augmenter``: a dict's pixels go to the device as they are (uint8 stays uint8) and
+    ``ops.augment_image`` resamples, crops, mirrors and normalises them in one launch into the network input of the
+    augmenter's crop size; key points and centre go through the same map on the host and every target is made from them at
+    that size.  One draw per sample, per clip for (B, T, ...) items.  Optional entries ``valid_hw`` (B, 2), the part of each
+    padded image that holds pixels, and ``scale`` (B,), the person scale RandomResized divides by.  The reference's tuples
+    arrive already rendered, so ``augment`` with a tuple raises ValueError."""
+
+    def __init__(self, device, stride: float = 8, sigma: float = 3.0, center_sigma: float = 3.0, bbox: bool = False,
+                 augment=None):
         self.dev, self.stride, self.sigma, self.csigma = torch.device(device), stride, sigma, center_sigma
         self.bbox = bool(bbox)
+        self.augment = augment
 
     def __call__(self, item):
         if isinstance(item, dict):
             px = item["pixels"].to(self.dev)
             lead = px.shape[:-3]
             h, w = px.shape[-3], px.shape[-2]
-            x = ops.normalize_image(px.reshape((-1, h, w, 3)).float())
             k = np.asarray(item["kpts"], dtype=np.float64)
+            center = item["center"]
+            if self.augment is not None:
+                frames = int(np.prod(lead[1:])) if len(lead) > 1 else 1
+                valid = item.get("valid_hw")
+                inv, k, center, _, _ = self.augment((h, w) if valid is None else np.asarray(valid), k, center, item.get("scale"))
+                if valid is not None and frames > 1:
+                    valid = np.repeat(np.asarray(valid).reshape(-1, 2), frames, axis=0)
+                if px.dtype not in (torch.uint8, torch.float32):
+                    px = px.float()
+                x = ops.augment_image(px.reshape((-1, h, w, px.shape[-1])), inv, self.augment.crop, valid_hw=valid,
+                                      frames_per_map=frames)
+                h, w = self.augment.crop
+            else:
+                x = ops.normalize_image(px.reshape((-1, h, w, 3)).float())
             heat = ops.make_heatmaps(k.reshape((-1,) + k.shape[-2:]), h, w, self.stride, self.sigma, self.dev)
-            c = np.asarray(item["center"], dtype=np.float64).reshape(-1, 2)
+            c = np.asarray(center, dtype=np.float64).reshape(-1, 2)
             cm = ops.make_centermaps(c, h, w, self.csigma, self.dev)
             out = (x.reshape(lead + x.shape[1:]), heat.reshape(lead + heat.shape[1:]), cm.reshape(lead + cm.shape[1:]))
             if self.bbox:
                 box = ops.make_box_maps(k.reshape((-1,) + k.shape[-2:]), h, w, self.stride, self.dev)
                 out += (box.reshape(lead + box.shape[1:]),)
             return out
+        if self.augment is not None:
+            raise ValueError("augment needs raw pixels and annotations (a dict item); the reference's tuples are already rendered")
         inp, heat, cm = item[0], item[1], item[2]
         if self.bbox:
             if len(item) < 6:
                 raise ValueError(f"bbox=True needs the loader's six-entry sample (the box maps last), got {len(item)} entries")
             return inp.to(self.dev), heat.to(self.dev), cm.to(self.dev), item[5].to(self.dev)
         return inp.to(self.dev), heat.to(self.dev), cm.to(self.dev)
+
+
+def _augmenter(args, dataset: str, size: int):
+    """``args.augment`` (default off) -> the training batcher's ``Augmenter`` at the reference's settings (RandomResized(),
+    RandomRotate(40), RandomCrop(size), RandomHorizontalFlip() where the reference has a left / right table), or None."""
+    if not getattr(args, "augment", False):
+        return None
+    from .augment import SWAP_PAIRS, Augmenter
+    return Augmenter(dataset, crop=size, flip_prob=0.5 if dataset in SWAP_PAIRS else 0.0, seed=_rank_seed(3))
 
 
 def _rank_seed(base: int) -> int:
@@ -258,7 +291,10 @@ class Trainer(_TrainerBase):
     makes the five box target maps.  The reference has no training loop for this head (it keeps the head as comments), so
     the loss is this project's decision: ``criterion(heat, heatmap) + criterion(box, boxmap)``, two ``MSELoss`` calls
     summed the way the video driver sums its per-frame criterion calls (uniposeLSTM.py:118-133), one backward.  PCK / PCKh
-    and ``test`` read the joint maps only."""
+    and ``test`` read the joint maps only.
+
+    ``args.augment`` (default off): the TRAINING batcher augments on the device (``augment.Augmenter`` seeded per rank,
+    ``ops.augment_image``); validation and ``test`` never do."""
     batch_size = 8
     sigma = 3
 
@@ -277,6 +313,8 @@ class Trainer(_TrainerBase):
             self.numClasses, self.batch_size, getattr(args, "val_batches", 2), size, seed=2)
         self.bbox = bool(getattr(args, "bbox", False))
         self.batcher = DeviceBatcher(dev, self.stride, self.sigma, bbox=self.bbox)
+        aug = _augmenter(args, args.dataset, size)              # the training batcher only; validation never augments
+        self.train_batcher = DeviceBatcher(dev, self.stride, self.sigma, bbox=self.bbox, augment=aug) if aug is not None else self.batcher
         model = unipose(args.dataset, num_classes=self.numClasses, backbone="resnet", output_stride=16, sync_bn=True,
                         freeze_bn=False, stride=self.stride, bbox=self.bbox)
         self._setup(model, args, dev)
@@ -300,7 +338,7 @@ class Trainer(_TrainerBase):
         i = -1
         for i, item in enumerate(bar):
             self._lr_step()
-            batch = self.batcher(item)
+            batch = self.train_batcher(item)
             self.optimizer.zero_grad()
             _, loss = self._forward_loss(batch)
             train_loss += loss.item()
@@ -342,7 +380,7 @@ class Trainer(_TrainerBase):
 
 
 class VideoTrainer(_TrainerBase):
-    """UniPose-LSTM (reference ``uniposeLSTM.py:36-260``)."""
+    """UniPose-LSTM (reference ``uniposeLSTM.py:36-260``).  ``args.augment`` as for ``Trainer``, one draw per clip."""
     batch_size = 1
     sigma = 1                      # uniposeLSTM.py:53
     frame_memory = 5               # uniposeLSTM.py:43
@@ -360,6 +398,8 @@ class VideoTrainer(_TrainerBase):
         self.train_loader = train_loader if train_loader is not None else mk(getattr(args, "train_batches", 2), _rank_seed(1))
         self.val_loader = val_loader if val_loader is not None else mk(getattr(args, "val_batches", 1), 2)
         self.batcher = DeviceBatcher(dev, self.stride, self.sigma)
+        aug = _augmenter(args, args.dataset, size)              # one draw per clip; validation never augments
+        self.train_batcher = DeviceBatcher(dev, self.stride, self.sigma, augment=aug) if aug is not None else self.batcher
         model = unipose_lstm(num_classes=self.numClasses, backbone="resnet", output_stride=16, sync_bn=True,
                              freeze_bn=False, stride=self.stride)
         model.batch_frames = True      # this loop always walks all frames of a clip: trunk once per clip batch, not per frame
@@ -394,7 +434,7 @@ class VideoTrainer(_TrainerBase):
         i = -1
         for i, item in enumerate(bar):
             self._lr_step()
-            input_var, heatmap_var, centermap_var = self.batcher(item)
+            input_var, heatmap_var, centermap_var = self.train_batcher(item)
             self.optimizer.zero_grad()
             loss = self._unroll(input_var, heatmap_var, centermap_var)
             train_loss += loss.item()
