@@ -66,7 +66,13 @@ typedef struct {
  *   v = acc;  if(scale) v = v*scale[k] + shift[k];   (folded eval-mode BatchNorm, K7)
  *   if(bias) v += bias[k];  if(residual) v += residual[pixel*ldr + k];  if(relu) v = max(v,0)
  * `stats` != NULL asks for per-(row-tile, channel) Welford partials {count, mean, M2} of the RAW
- * accumulator (train-mode BatchNorm statistics, K7); it excludes scale/bias/residual/relu. */
+ * accumulator (train-mode BatchNorm statistics, K7).  A call that passes `stats` TOGETHER with scale, bias, residual or relu
+ * is refused with UP_ERR_INVALID and launches nothing (the statistics are not "taken before" such an epilogue: the
+ * combination does not exist).  In bf16 storage the partials come from the fp32 accumulators, not from the rounded y.
+ * Also refused with UP_ERR_INVALID before any launch: scale without shift; a residual with ldr < K; `fold` without `stats`
+ * (or without gamma / beta / its four outputs, or with only one of the running statistics); UP_MATH_BF16S_F32OUT with a
+ * residual or with stats.  Of every output pixel only lanes [0, K) are written (in bf16 storage at most up to the next
+ * multiple of 32): the lanes behind them, up to ldy, keep what they held. */
 /* ABI 10: BatchNorm finalize FOLDED into the launch that writes `stats`.  Every workgroup takes a ticket after publishing its
  * partial row; the last arriver merges the partials in a fixed order (deterministic; the same bits as up_bn_finalize on the same
  * stats) and writes mean / invstd / scale / shift (+ the running-statistics update) — no up_bn_finalize launch on the critical
@@ -182,7 +188,12 @@ int up_conv2d_bwd_data(const up_conv_desc* d, const float* dy, const float* w_dg
  *    and its ReLU mask is applied here (bit row * C + c of that layer's sign bits), so that layer's backward need not write
  *    dz * [z > 0] as a tensor of its own (threshold_backward's output).
  * up_conv2d_bwd_data_tiles_math(d, math) = rows of `partial`, and > 0 exactly when the launch of `d` runs on a kernel that
- * supports the two extras (math = UP_MATH_F32 or UP_MATH_BF16S); with 0 use the plain entry points (add only). */
+ * supports the two extras (math = UP_MATH_F32 or UP_MATH_BF16S); with 0 use the plain entry points (add only).
+ * Both sums are taken on the STORED dx (in bf16 storage: after the rounding to bf16, also where an addend joined in fp32), like a
+ * separate reduction pass that reads dx back.  Refused before any launch: add_relu_bits without add, dgamma without dbeta (or the
+ * reverse), bn->C != d->C or bn->ld < d->C (UP_ERR_INVALID); a slot or add_relu_bits where up_conv2d_bwd_data_tiles_math is 0
+ * (stride 2, Kp % 32 != 0, more than 32 taps), groups > 1 with UP_MATH_BF16S or where up_conv2d_bwd_data_tiles_grouped is 0
+ * (UP_ERR_UNSUPPORTED).  With bn_fold switched off, or groups > 1 and gsum == NULL, dgamma / dbeta / gsum are not written. */
 /* Row groups (ABI 8): `groups` equal batches stacked along N that must keep separate BatchNorm statistics (the frames of the video
  * model's batched trunk).  Every group is tiled on its own, so no row tile straddles two groups and stats is
  * [groups][up_conv_stats_tiles_grouped(d, groups)][K][3] — the layout up_bn_finalize_groups merges; no extra pass over y
