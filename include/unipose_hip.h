@@ -486,6 +486,45 @@ int up_heatmap_argmax(const float* hm, int B, int J, int H, int W,
 int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W,
                       int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream);
 
+/* ---- the evaluation protocol around the forward: flip test and final_preds (ABI 10 additions) ----
+ * What published PCKh numbers of this family of networks add to get_max_preds (utils/extra_utils, vendored from pytorch-pose):
+ * the flip test (transforms.py:22-43 flip_back, :70-76 fliplr), the quarter-pixel refinement (evaluation.py:75-88 final_preds)
+ * and the way back to the source image (transforms.py:79-125 get_transform / transform / transform_preds).
+ *
+ * up_nchw_to_nhwc_flip: up_nchw_to_nhwc with the mirror folded in, y[n,h,w,c] = x[n,c,h,W-1-w]; pad channels C <= c < ldy are
+ * written as zeros exactly as there.  Equal bits to up_nchw_to_nhwc of the mirrored tensor; the same refusals.
+ *
+ * up_flip_merge: out[b,j,y,x] = 0.5f * (a[b,j,y,x] + f[b,perm[j],y,W-1-x]) — one float32 add, one multiply by 0.5, each rounded
+ * once.  The MEAN, where pytorch-pose's drivers take the sum: the argmax is the same and the values stay heat-maps.  a and f
+ * share three element strides, out has its own, each addressing a map as up_heatmap_decode's do (NHWC as a convolution leaves
+ * it, pad channels never read or written, or NCHW).  perm_host: J int32 on the HOST, checked here and passed to the kernel by
+ * value (256 bytes); it need not be an involution.  out may be a when the strides are equal; out must not overlap f.
+ * UP_ERR_INVALID (nothing launched): a null pointer, a size or a stride <= 0, a perm entry outside 0..J-1, out == f (mirrored
+ * reads cross threads), out == a with other strides, the offset of the last element beyond int32.  UP_ERR_UNSUPPORTED: J > 256.
+ *
+ * up_final_preds: one wavefront per map, like up_heatmap_argmax.  Per map (b, j):
+ *   1. i = the first-max flat index (lowest index wins ties, a NaN wins); maxvals[b,j] = the maximum;
+ *   2. x = i % W + 1, y = i / W + 1 as float32, both 0 unless max > 0 (a NaN maximum masks to 0 as maxval.gt(0) does);
+ *   3. px = (int)x, py = (int)y; if 1 < px < res0 and 1 < py < res1 and px < W and py < H (the last two hold wherever the
+ *      reference does not raise IndexError and keep every read inside the map):
+ *      x += 0.25f * sgn(hm[py-1][px] - hm[py-1][px-2]), y += 0.25f * sgn(hm[py][px-1] - hm[py-2][px-1]), sgn(p - q) computed as
+ *      (p > q) - (p < q): the sign of the float32 difference for finite values, and defined for infinities;
+ *   4. x += 0.5f, y += 0.5f: coords_xy (B,J,2), may be NULL;
+ *   5. inv (device, (B,2,3) float64 row-major: the first two rows of np.linalg.inv(get_transform(center, scale, res))):
+ *      p0 = (double)x - 1, p1 = (double)y - 1, v_i = (inv[b][i][0] * p0 + inv[b][i][1] * p1) + inv[b][i][2], every product and
+ *      sum rounded on its own (no FMA), preds_xy[b,j,i] = (float)((long long)v_i + 1): truncation towards zero like astype(int).
+ *      |v_i| >= 2^31 is outside the contract: the launch stays safe, the value is unspecified.  inv == NULL: preds = coords.
+ * res0 bounds x and res1 bounds y: the reference's own order in final_preds, and the OPPOSITE of get_transform, where res[1]
+ * scales x — so on non-square maps the reference only works with res = [W, H].  Kept as it is.
+ * Strides as in up_heatmap_decode.  UP_ERR_INVALID (nothing launched): null hm / preds_xy / maxvals, a size, a stride or a res
+ * <= 0, H * W or the offset of the last element beyond int32. */
+int up_nchw_to_nhwc_flip(const float* x, float* y, int N, int C, int H, int W, int ldy, void* stream);
+int up_flip_merge(const float* a, const float* f, int64_t in_stride_b, int64_t in_stride_j, int64_t in_stride_p, int B, int J,
+                  int H, int W, const int32_t* perm_host, float* out, int64_t out_stride_b, int64_t out_stride_j,
+                  int64_t out_stride_p, void* stream);
+int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W, int res0,
+                   int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals, void* stream);
+
 /* ---- training targets and input normalisation (the step BEFORE the path) ----
  * up_make_heatmaps: lsp_lspet_data.py:224-236 / mpii_data.py:165-175.  kpt_xy (B,K,2) float64 pixel coordinates of the
  * input image; joint k of sample b is centred at int(coordinate) / stride on the H x W map; values
@@ -633,7 +672,21 @@ int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int
  *                                 decoder.last_conv.8, on the heat-maps' own grid (the one the reference decodes on): count, status
  *                                 (batch), kpts (batch, max_persons, njoints + 5, 2) as documented there.  Channel arguments
  *                                 outside out_channels, max_persons outside 1 .. UP_PERSONS_CAP or a null pointer are
- *                                 UP_ERR_INVALID before anything is launched. */
+ *                                 UP_ERR_INVALID before anything is launched.
+ * The evaluation protocol (flip test, final_preds; see up_flip_merge / up_final_preds) has three programs more.  They need a
+ * larger workspace, up_unipose_plan_flip_workspace() bytes, because the flip test keeps the first pass's heat-maps while the
+ * trunk runs again; up_unipose_plan_workspace() is what it was.  All work on the heat-maps' own grid ceil(H/8) x ceil(W/8).
+ *   up_unipose_flip_forward       the trunk on x and on the mirrored x (up_nchw_to_nhwc_flip) over the same activations — every
+ *                                 convolution launch is the one up_unipose_forward makes — then up_flip_merge with perm_host
+ *                                 (out_channels int32 on the host) into heat_nchw (batch, out_channels, ceil(H/8), ceil(W/8)):
+ *                                 equal bits to merging up_unipose_forward of x and of the mirrored x.
+ *   up_unipose_final_preds        the same, merged in place, then up_final_preds straight from the NHWC maps: preds_xy, coords_xy
+ *                                 (may be NULL), maxvals (batch, out_channels[, 2]); inv (device, (batch,2,3) float64) may be NULL.
+ *                                 perm_host == NULL: one pass, no flip test (up_unipose_plan_workspace() bytes suffice).
+ * A perm entry outside 0 .. out_channels-1, res <= 0, a null pointer, unset weights or a too-small workspace are refused before
+ * anything is launched.  up_unipose_plan_program_workspace(plan, k): the need of program k alone, in the order of this comment
+ * (0 forward, 1 upsampled, 2 keypoints, 3 persons, 4 flip_forward, 5 final_preds with and 6 without the flip test), 0 for any
+ * other k: up_unipose_plan_workspace() is the largest of 0..3, up_unipose_plan_flip_workspace() of 4..6. */
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
     int32_t batch, height, width;   /* input (batch, 3, height, width) */
@@ -655,6 +708,13 @@ int up_unipose_keypoints(up_unipose_plan* plan, const float* x_nchw, int out_h, 
                          float* maxvals, void* workspace, size_t workspace_bytes, void* stream);
 int up_unipose_persons(up_unipose_plan* plan, const float* x_nchw, int box_ch0, int joint_ch0, int njoints, int max_persons,
                        int32_t* count, int32_t* status, int32_t* kpts, void* workspace, size_t workspace_bytes, void* stream);
+size_t up_unipose_plan_flip_workspace(const up_unipose_plan* plan);
+size_t up_unipose_plan_program_workspace(const up_unipose_plan* plan, int program);
+int up_unipose_flip_forward(up_unipose_plan* plan, const float* x_nchw, const int32_t* perm_host, float* heat_nchw, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int up_unipose_final_preds(up_unipose_plan* plan, const float* x_nchw, const int32_t* perm_host, const double* inv, int res0,
+                           int res1, float* preds_xy, float* coords_xy, float* maxvals, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- whole-clip and per-frame inference entry of UniPose-LSTM (ABI 10 additions) ----------------------------------------
  * The video network (model/uniposeLSTM.py:67-138: the image trunk with the video WASP, ConvLSTM, five-convolution head) with

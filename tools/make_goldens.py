@@ -909,6 +909,121 @@ def g20_augment():
     save("g20_augment.npz", tags=np.array(tags), **out)
 
 
+def g21_final_preds():
+    """G21: the evaluation protocol of utils/extra_utils (vendored pytorch-pose).  The genuine evaluation.py / transforms.py are
+    loaded by file path under a private package name, with this project's stand-ins for what is absent here: tools/cv2_standin.py
+    as `cv2`, empty modules as `matplotlib.pyplot` and `scipy.misc` (nothing recorded touches them).  Recorded:
+      c<k>_*   per map shape: hm (B,J,H,W) random + planted maps, get_preds, centres / scales as float32 tensors (c32, s32) and as
+               float64 arrays (c64, s64); stacked over the R values of res (R,2): get_transform and its inverse for both kinds
+               (T32, Ti32, T64, Ti64), final_preds (fp32, fp64) and ok (R,) — False, and final_preds zeros, where the reference
+               raises IndexError; those are listed in index_error (H, W, res0, res1);
+      x_*      the exact-integer case: res 16, scale 16 * 4 / 200, integer centres: every transformed value an exact integer;
+      fb<k>_*  flip_back (MPII, 16 channels): in, out."""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import cv2_standin
+    sys.modules["cv2"] = cv2_standin
+    for name in ("matplotlib", "matplotlib.pyplot", "scipy.misc"):
+        if name not in sys.modules:
+            try:
+                __import__(name)
+            except Exception:
+                sys.modules[name] = types.ModuleType(name)
+    import scipy
+    import scipy.io  # noqa: F401
+    if not hasattr(scipy, "misc"):
+        scipy.misc = sys.modules["scipy.misc"]
+    if "matplotlib.pyplot" in sys.modules and not hasattr(sys.modules["matplotlib"], "pyplot"):
+        sys.modules["matplotlib"].pyplot = sys.modules["matplotlib.pyplot"]
+    base = os.path.join(REF, "utils", "extra_utils")
+    pkg = types.ModuleType("ref_extra_utils")
+    pkg.__path__ = [base]
+    sys.modules["ref_extra_utils"] = pkg
+    mods = {}
+    for name in ("misc", "imutils", "transforms", "evaluation"):
+        spec = importlib.util.spec_from_file_location("ref_extra_utils." + name, os.path.join(base, name + ".py"))
+        m = importlib.util.module_from_spec(spec)
+        sys.modules[spec.name] = m
+        spec.loader.exec_module(m)
+        mods[name] = m
+    E, T = mods["evaluation"], mods["transforms"]
+    rng = np.random.default_rng(21)
+    out, raised = {}, []
+
+    def planted(h, w):
+        maps = []
+        small = lambda: (rng.standard_normal((h, w)) * 0.1).astype(np.float32)
+        maps.append((-np.abs(rng.standard_normal((h, w))) - 0.5).astype(np.float32))       # all negative
+        maps.append(np.zeros((h, w), np.float32))                                          # all zero
+        maps.append(np.full((h, w), 0.7, np.float32))                                      # a plateau: the first index
+        spots = [(0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1),                           # the corners
+                 (h // 2, 0), (h // 2, max(w - 2, 0)), (h // 2, w - 1),                    # px == 1, res0 - 1, res0
+                 (0, w // 2), (max(h - 2, 0), w // 2), (h - 1, w // 2)]                    # py == 1, res1 - 1, res1
+        for y, x in spots:
+            m = small()
+            m[y, x] = 5.0
+            maps.append(m)
+        m = small()                                                                        # equal neighbours: sign 0
+        y, x = h // 2, w // 2
+        for yy, xx in ((y - 1, x), (y + 1, x), (y, x - 1), (y, x + 1)):
+            if 0 <= yy < h and 0 <= xx < w:
+                m[yy, xx] = 1.0
+        m[y, x] = 5.0
+        maps.append(m)
+        m = rng.standard_normal((h, w)).astype(np.float32)                                 # a NaN
+        m[h // 2, w // 2] = np.nan
+        maps.append(m)
+        return maps
+
+    def record(tag, hm, res_list, c64, s64):
+        b, _, h, w = hm.shape
+        c32, s32 = torch.tensor(c64, dtype=torch.float32), torch.tensor(s64, dtype=torch.float32)
+        t = torch.from_numpy(hm)
+        out.update({tag + "_hm": hm, tag + "_getpreds": E.get_preds(t.clone()).numpy(), tag + "_c32": c32.numpy(),
+                    tag + "_s32": s32.numpy(), tag + "_c64": c64, tag + "_s64": s64})
+        acc = {k: [] for k in ("T32", "Ti32", "T64", "Ti64", "fp32", "fp64")}
+        ok = []
+        for res in res_list:
+            for kind, c, s in (("32", c32, s32), ("64", c64, s64)):
+                mats = [T.get_transform(c[i], s[i], res) for i in range(b)]
+                acc["T" + kind].append(np.stack(mats))
+                acc["Ti" + kind].append(np.stack([np.linalg.inv(m) for m in mats]))
+                try:
+                    got = E.final_preds(t.clone(), c, s, res)
+                    assert got.dtype == torch.float32 and tuple(got.shape) == (b, hm.shape[1], 2)
+                    got = got.numpy()
+                except IndexError:
+                    got = np.zeros((b, hm.shape[1], 2), np.float32)
+                    if kind == "32":
+                        raised.append([h, w, res[0], res[1]])
+                if kind == "32":
+                    ok.append([h, w, res[0], res[1]] not in raised)
+                acc["fp" + kind].append(got)
+        out[tag + "_res"] = np.array(res_list, dtype=np.int64)
+        out[tag + "_ok"] = np.array(ok)
+        out.update({tag + "_" + k: np.stack(v) for k, v in acc.items()})
+
+    shapes = [(1, 1), (2, 5), (3, 3), (7, 9), (9, 7), (8, 8), (5, 13), (12, 12)]
+    B = 2
+    for k, (h, w) in enumerate(shapes):
+        hm = np.stack([np.stack([rng.standard_normal((h, w)).astype(np.float32) for _ in range(2)] + planted(h, w))
+                       for _ in range(B)])
+        c64 = rng.uniform(60.0, 300.0, (B, 2))
+        s64 = rng.uniform(0.4, 2.5, B)
+        res_list = [[w, h], [h, w], [w + 3, h + 3], [max(w - 2, 1), max(h - 2, 1)]]
+        record("c%d" % k, hm, res_list, c64, s64)
+    # the exact-integer case
+    hm = rng.standard_normal((4, 4, 16, 16)).astype(np.float32)
+    record("x", hm, [[16, 16]], rng.integers(2, 120, (4, 2)).astype(np.float64), np.full(4, 16 * 4 / 200))
+    for k, shape in enumerate(((2, 16, 4, 6), (1, 16, 5, 5))):
+        f = rng.standard_normal(shape).astype(np.float32)
+        out["fb%d_in" % k] = f
+        out["fb%d_out" % k] = T.flip_back(torch.from_numpy(f.copy())).numpy()
+    out["index_error"] = np.array(raised, dtype=np.int64).reshape(-1, 4)
+    print("g21: IndexError at", raised)
+    save("g21_final_preds.npz", shapes=np.array(shapes, dtype=np.int64), **out)
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -922,10 +1037,10 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
                g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect,
-               g19=g19_box_targets, g20=g20_augment)
+               g19=g19_box_targets, g20=g20_augment, g21=g21_final_preds)
     for w in which:
         fns[w]()

@@ -26,6 +26,9 @@ def parse_args(argv=None):
     p.add_argument("--bbox", action="store_true", help="train the optional box head too (model/unipose.py:34-35; default off)")
     p.add_argument("--augment", action="store_true",
                    help="augment the training batches on the device (resize, rotate, crop, mirror as utils/Mytransforms.py; default off)")
+    p.add_argument("--flip-test", dest="flip_test", action="store_true",
+                   help="validate with the flip test of utils/extra_utils: mean of the maps and the mirrored-back maps of the "
+                        "mirrored batch (default off)")
     return p.parse_args(argv)
 
 

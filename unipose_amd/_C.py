@@ -143,6 +143,9 @@ SIGNATURES = {
     "up_lstm_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _i, _p]),
     "up_heatmap_argmax": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "up_heatmap_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "up_nchw_to_nhwc_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "up_flip_merge": (_i, [_p, _p, _i64, _i64, _i64, _i, _i, _i, _i, C.POINTER(C.c_int32), _p, _i64, _i64, _i64, _p]),
+    "up_final_preds": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "up_make_heatmaps": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p]),
     "up_make_box_maps": (_i, [_p, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p]),
     "up_make_gaussian_maps": (_i, [_p, _i, _i, _i, C.c_double, _p, _p]),
@@ -163,6 +166,10 @@ SIGNATURES = {
     "up_unipose_forward_upsampled": (_i, [_p, _p, _p, _p, _sz, _p]),
     "up_unipose_keypoints": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_unipose_persons": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_plan_flip_workspace": (_sz, [_p]),
+    "up_unipose_plan_program_workspace": (_sz, [_p, _i]),
+    "up_unipose_flip_forward": (_i, [_p, _p, C.POINTER(C.c_int32), _p, _p, _sz, _p]),
+    "up_unipose_final_preds": (_i, [_p, _p, C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_clip_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),

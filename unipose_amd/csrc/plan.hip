@@ -11,7 +11,7 @@
 // The launches, their order, their descriptors and their epilogues are exactly those of the drop-in module's folded inference
 // forward (unipose_amd/unipose.py + modules.py after checkpoint.load_folded), so the two produce equal bits
 // (tests/test_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
-// The image plan keeps four programs over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
+// The image plan keeps four programs (and the three of the evaluation protocol, see ImageForm) over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
 // input size as the module does at stride != 8 (up_unipose_forward_upsampled), the joints decoded straight from the NHWC
 // output of the last convolution (up_unipose_keypoints -> up_heatmap_decode; tests/test_heat_decode_*.py), and the persons of
 // the box head decoded from the same NHWC output (up_unipose_persons -> up_persons_decode; tests/test_persons_*.py).
@@ -74,6 +74,8 @@ enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW,
     DECODE,                // key points straight from the NHWC heat-maps (up_heatmap_decode), on the grid the call names
     PERSONS,               // the multi-person decode straight from the NHWC heat-maps (up_persons_decode), on their own grid
+    // the evaluation protocol (ABI 10 additions): the mirrored layout pass, the flip test's combine step, final_preds from NHWC
+    TO_NHWC_FLIP, MERGE, FINAL,
     // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL
 };
@@ -343,7 +345,11 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
 // stride 8; UPSAMPLED: at stride != 8, the heat-maps bilinearly up-sampled to the input size before the layout pass
 // (model/unipose.py:31-32; unipose_amd/unipose.py forward); KEYPOINTS: the trunk, then up_heatmap_decode on its NHWC output;
 // PERSONS_FORM: the trunk, then up_persons_decode on its NHWC output.
-enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM };
+// The evaluation protocol (utils/extra_utils): FLIP_HEAT: the trunk on x and on the mirrored x (up_nchw_to_nhwc_flip) over the same
+// activations — every convolution launch is the one HEAT_MAPS makes — the first pass's heat-maps staying alive through the second,
+// then up_flip_merge into the caller's NCHW tensor; FLIP_PREDS: the same, merged in place (NHWC), then up_final_preds; PREDS: one
+// pass, then up_final_preds.  All three work on the heat-maps' own grid.
+enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM, FLIP_HEAT, FLIP_PREDS, PREDS, IMAGE_FORMS };
 
 static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
     const int n = c.batch;
@@ -360,6 +366,36 @@ static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
         p.push(op);
     }
     x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
+    if (form == FLIP_HEAT || form == FLIP_PREDS) {
+        int h2 = c.height, w2 = c.width;
+        Ref m;
+        m.id = p.tensor(n, h2, w2, 4);
+        Op op;
+        op.kind = TO_NHWC_FLIP;
+        op.out = m;
+        op.ext = X;
+        op.n = n; op.c = 3;
+        p.push(op);
+        m = trunk(p, m, n, h2, w2, c.output_stride, c.out_channels, false);
+        op = Op();
+        op.kind = MERGE;
+        op.in = x; op.aux = m;
+        if (form == FLIP_PREDS) op.out = x;      // in place: out == a with equal strides
+        op.ext = HEAT;
+        op.n = n; op.c = c.out_channels;
+        p.push(op);
+    }
+    if (form == FLIP_PREDS || form == PREDS) {
+        Op op;
+        op.kind = FINAL;
+        op.in = x;
+        op.n = n; op.c = c.out_channels;
+        p.push(op);
+    }
+    if (form == FLIP_HEAT || form == FLIP_PREDS || form == PREDS) {
+        p.layout();
+        return UP_OK;
+    }
     if (form == KEYPOINTS || form == PERSONS_FORM) {
         Op op;
         op.kind = form == KEYPOINTS ? DECODE : PERSONS;
@@ -523,6 +559,10 @@ struct Io {
     int32_t* count = nullptr;
     int32_t* status = nullptr;
     int32_t* kpts = nullptr;
+    const int32_t* perm = nullptr;   // MERGE: the channel permutation (host); FINAL: the arguments and outputs of up_final_preds
+    const double* inv = nullptr;
+    int res0 = 0, res1 = 0;
+    float* coords = nullptr;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -577,6 +617,23 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             e = up_persons_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c, T_(op.in).h,
                                   T_(op.in).w, io.box_ch0, io.joint_ch0, io.njoints, io.max_persons, io.count, io.status, io.kpts, stream);
             break;
+        case TO_NHWC_FLIP:
+            e = up_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            break;
+        case MERGE: {
+            const Tensor& t = T_(op.in);
+            const int64_t sb = (int64_t)t.h * t.w * t.c;
+            if (op.out.id >= 0)
+                e = up_flip_merge(ptr(op.in), ptr(op.aux), sb, 1, t.c, op.n, op.c, t.h, t.w, io.perm, ptr(op.out), sb, 1, t.c, stream);
+            else
+                e = up_flip_merge(ptr(op.in), ptr(op.aux), sb, 1, t.c, op.n, op.c, t.h, t.w, io.perm, io.out(op.ext),
+                                  (int64_t)op.c * t.h * t.w, (int64_t)t.h * t.w, 1, stream);
+            break;
+        }
+        case FINAL:
+            e = up_final_preds(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c, T_(op.in).h,
+                               T_(op.in).w, io.res0, io.res1, io.inv, io.preds, io.coords, io.maxvals, stream);
+            break;
         case POOL:
             e = up_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.a, op.b, T_(op.out).h, T_(op.out).w, stream);
             break;
@@ -614,7 +671,10 @@ struct up_unipose_plan {
     up_unipose_config cfg;
     Plan p;                    // HEAT_MAPS; its convolutions are the listed ones and own the weight store
     Plan up, kp, ps;           // UPSAMPLED, KEYPOINTS, PERSONS_FORM: the same trunk, so the same convolutions in the same order
-    size_t ws_bytes = 0;       // the largest of the four
+    Plan fh, fp, pr;           // FLIP_HEAT, FLIP_PREDS (the trunk twice: every convolution name twice), PREDS
+    size_t ws_bytes = 0;       // the largest of the first four
+    size_t flip_ws_bytes = 0;  // the largest of the last three
+    Plan* prog(int form) { Plan* const all[up::plan::IMAGE_FORMS] = {&p, &up, &kp, &ps, &fh, &fp, &pr}; return all[form]; }
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
@@ -626,13 +686,13 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
-    Plan* const progs[4] = {&pl->p, &pl->up, &pl->kp, &pl->ps};
-    for (int f = 0; f < 4; ++f) {
-        if (int e = up::plan::build(*progs[f], pl->cfg, static_cast<plan::ImageForm>(f))) {
+    for (int f = 0; f < plan::IMAGE_FORMS; ++f) {
+        if (int e = up::plan::build(*pl->prog(f), pl->cfg, static_cast<plan::ImageForm>(f))) {
             delete pl;
             return e;
         }
-        pl->ws_bytes = std::max(pl->ws_bytes, progs[f]->ws_bytes);
+        size_t& need = f < plan::FLIP_HEAT ? pl->ws_bytes : pl->flip_ws_bytes;
+        need = std::max(need, pl->prog(f)->ws_bytes);
     }
     // plan-owned device memory: one forward weight image (+ bias) per DISTINCT parameter (wasp.conv2 is applied twice)
     for (size_t i = 0; i < pl->p.convs.size(); ++i) {
@@ -651,11 +711,15 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
             UP_REQUIRE(false, UP_ERR_INVALID, "unipose_plan_create: out of device memory");
         }
     }
-    for (Plan* other : {&pl->up, &pl->kp, &pl->ps})
-        for (size_t i = 0; i < other->convs.size(); ++i) {
-            other->convs[i].w_fwd = pl->p.convs[i].w_fwd;
-            other->convs[i].bias = pl->p.convs[i].bias;
-        }
+    // the other programs share the store by NAME (the flip programs run the trunk twice)
+    for (int f = 1; f < plan::IMAGE_FORMS; ++f)
+        for (plan::Conv& cv : pl->prog(f)->convs)
+            for (const plan::Conv& own : pl->p.convs)
+                if (own.name == cv.name) {
+                    cv.w_fwd = own.w_fwd;
+                    cv.bias = own.bias;
+                    break;
+                }
     *out = pl;
     return UP_OK;
 }
@@ -701,6 +765,12 @@ extern "C" int up_unipose_plan_set_conv(up_unipose_plan* pl, int i, const float*
 }
 
 extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return pl ? pl->ws_bytes : 0; }
+
+extern "C" size_t up_unipose_plan_flip_workspace(const up_unipose_plan* pl) { return pl ? pl->flip_ws_bytes : 0; }
+
+extern "C" size_t up_unipose_plan_program_workspace(const up_unipose_plan* pl, int program) {
+    return pl && program >= 0 && program < plan::IMAGE_FORMS ? const_cast<up_unipose_plan*>(pl)->prog(program)->ws_bytes : 0;
+}
 
 static int image_ready(const up_unipose_plan* pl, const Plan& prog, const void* workspace, size_t ws_bytes, const char* what) {
     for (const plan::Conv& cv : pl->p.convs)
@@ -772,6 +842,48 @@ extern "C" int up_unipose_persons(up_unipose_plan* pl, const float* x_nchw, int 
     io.status = status;
     io.kpts = kpts;
     return plan::run(pl->ps, io, static_cast<unsigned char*>(workspace), stream, "unipose_persons");
+}
+
+// the channel permutation of a flip-test call: refused here, before the first launch of the program
+static int perm_ok(const up_unipose_plan* pl, const int32_t* perm, const char* what) {
+    const int C = pl->cfg.out_channels;
+    UP_REQUIRE(C <= 256, UP_ERR_UNSUPPORTED, "%s: %d output channels (up_flip_merge takes up to 256)", what, C);
+    for (int j = 0; j < C; ++j)
+        UP_REQUIRE(perm[j] >= 0 && perm[j] < C, UP_ERR_INVALID, "%s: perm[%d] = %d outside 0..%d", what, j, (int)perm[j], C - 1);
+    return UP_OK;
+}
+
+extern "C" int up_unipose_flip_forward(up_unipose_plan* pl, const float* x_nchw, const int32_t* perm_host, float* heat_nchw,
+                                       void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && perm_host && heat_nchw && workspace, UP_ERR_INVALID, "unipose_flip_forward: null argument");
+    if (int e = perm_ok(pl, perm_host, "unipose_flip_forward")) return e;
+    if (int e = image_ready(pl, pl->fh, workspace, ws_bytes, "unipose_flip_forward")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.perm = perm_host;
+    io.heat = heat_nchw;
+    return plan::run(pl->fh, io, static_cast<unsigned char*>(workspace), stream, "unipose_flip_forward");
+}
+
+extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, const int32_t* perm_host, const double* inv, int res0,
+                                      int res1, float* preds_xy, float* coords_xy, float* maxvals, void* workspace, size_t ws_bytes,
+                                      void* stream) {
+    UP_REQUIRE(pl && x_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_final_preds: null argument");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_final_preds: res %d, %d", res0, res1);
+    if (perm_host)
+        if (int e = perm_ok(pl, perm_host, "unipose_final_preds")) return e;
+    const Plan& prog = perm_host ? pl->fp : pl->pr;
+    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_final_preds")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.perm = perm_host;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_final_preds");
 }
 
 // ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------

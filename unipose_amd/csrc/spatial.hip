@@ -1012,6 +1012,115 @@ __global__ void __launch_bounds__(256) pck_kernel(const float* pred, const float
     }
 }
 
+// ---- the evaluation protocol around the forward: flip test and final_preds (utils/extra_utils; include/unipose_hip.h) ---------
+// up_nchw_to_nhwc with the mirror folded in: the NHWC pixel (h, w) takes the NCHW pixel (h, W - 1 - w); pad channels as there
+__global__ void __launch_bounds__(256) nchw_to_nhwc_flip_kernel(const float* x, float* y, int C, int W, int HW, int ld,
+                                                                int64_t npix) {
+    UP_GRID_STRIDE(i, npix) {
+        int64_t n = i / HW;
+        int hw = (int)(i - n * HW);
+        int h = hw / W, w = hw - h * W;
+        const float* src = x + n * C * HW + h * W + (W - 1 - w);
+        float* dst = y + i * ld;
+        for (int c = 0; c < ld; ++c) st1(dst + c, nchw_at(src, C, HW, c));
+    }
+}
+
+// The flip test's combine step: out[b, j, y, x] = 0.5f * (a[b, j, y, x] + f[b, perm[j], y, W - 1 - x]), one add and one multiply,
+// each rounded once.  One thread per element; JFAST: consecutive threads walk the channels of a pixel (an NHWC output), else the
+// pixels of a map (NCHW).  The permutation travels by value: 256 bytes of kernel arguments.
+struct FlipPerm {
+    uint8_t v[256];
+};
+template <bool JFAST>
+__global__ void __launch_bounds__(256) flip_merge_kernel(const float* a, const float* f, int64_t isb, int64_t isj, int64_t isp,
+                                                         int J, int H, int W, FlipPerm perm, float* out, int64_t osb, int64_t osj,
+                                                         int64_t osp, int64_t total) {
+    const int HW = H * W;
+    UP_GRID_STRIDE(i, total) {
+        int64_t b;
+        int j, pix;
+        if (JFAST) {
+            const int64_t bp = i / J;
+            j = (int)(i - bp * J);
+            b = bp / HW;
+            pix = (int)(bp - b * HW);
+        } else {
+            const int64_t bj = i / HW;
+            pix = (int)(i - bj * HW);
+            b = bj / J;
+            j = (int)(bj - b * J);
+        }
+        const int y = pix / W, x = pix - y * W;
+        const float va = a[b * isb + j * isj + pix * isp];
+        const float vf = f[b * isb + (int64_t)perm.v[j] * isj + (int64_t)(y * W + (W - 1 - x)) * isp];
+        out[b * osb + j * osj + pix * osp] = __fmul_rn(0.5f, va + vf);
+    }
+}
+
+// final_preds (utils/extra_utils/evaluation.py:75-97): one wavefront per (b, j) map like argmax_kernel, then lane 0 does the
+// quarter-pixel refinement and the way back through the (2, 3) float64 inverse of the crop transform; every product and sum
+// of that transform is rounded on its own, in numpy's order (no FMA).
+__global__ void __launch_bounds__(256) final_preds_kernel(const float* hm, int64_t sb, int64_t sj, int64_t sp, int maps, int J,
+                                                          int H, int W, int res0, int res1, const double* inv, float* preds,
+                                                          float* coords, float* maxvals) {
+    int map = blockIdx.x * 4 + (threadIdx.x >> 6);
+    int lane = threadIdx.x & 63;
+    if (map >= maps) return;
+    const int b = map / J, j = map - b * J;
+    const float* p = hm + b * sb + j * sj;
+    const int HW = H * W;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < HW; i += 64) {
+        float v = p[i * sp];
+        if (am_better(v, i, bv, bi)) {
+            bv = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        float ov = __shfl_down(bv, off);
+        int oi = __shfl_down(bi, off);
+        if (am_better(ov, oi, bv, bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    if (lane != 0) return;
+    maxvals[map] = bv;
+    float x = 0.f, y = 0.f;
+    if (bv > 0.f) {                 // a NaN maximum masks to 0 as maxval.gt(0) does
+        x = (float)(bi % W + 1);
+        y = (float)(bi / W + 1);
+    }
+    const int px = (int)x, py = (int)y;
+    // px < W and py < H hold wherever the reference does not raise IndexError: they keep the four reads inside the map
+    if (px > 1 && px < res0 && py > 1 && py < res1 && px < W && py < H) {
+        const float r = p[((py - 1) * W + px) * sp], l = p[((py - 1) * W + px - 2) * sp];
+        const float d = p[(py * W + px - 1) * sp], u = p[((py - 2) * W + px - 1) * sp];
+        x += 0.25f * (float)((r > l) - (r < l));
+        y += 0.25f * (float)((d > u) - (d < u));
+    }
+    x += 0.5f;
+    y += 0.5f;
+    if (coords) {
+        coords[map * 2] = x;
+        coords[map * 2 + 1] = y;
+    }
+    if (inv) {
+        const double* m = inv + (int64_t)b * 6;
+        const double p0 = (double)x - 1.0, p1 = (double)y - 1.0;
+        const double v0 = __dadd_rn(__dadd_rn(__dmul_rn(m[0], p0), __dmul_rn(m[1], p1)), m[2]);
+        const double v1 = __dadd_rn(__dadd_rn(__dmul_rn(m[3], p0), __dmul_rn(m[4], p1)), m[5]);
+        x = (float)((long long)v0 + 1);         // astype(int) truncates towards zero
+        y = (float)((long long)v1 + 1);
+    }
+    preds[map * 2] = x;
+    preds[map * 2 + 1] = y;
+}
+
 }  // namespace up
 
 using namespace up;
@@ -1032,6 +1141,12 @@ extern "C" int up_nchw_to_nhwc_t(const float* x, void* y, int N, int C, int H, i
 }
 extern "C" int up_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, int ldy, void* stream) {
     return up_nchw_to_nhwc_t(x, y, N, C, H, W, ldy, UP_DT_F32, stream);
+}
+extern "C" int up_nchw_to_nhwc_flip(const float* x, float* y, int N, int C, int H, int W, int ldy, void* stream) {
+    UP_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0 && ldy >= C, UP_ERR_INVALID, "nchw_to_nhwc_flip: bad argument");
+    int64_t npix = (int64_t)N * H * W;
+    UP_LAUNCH_1D(nchw_to_nhwc_flip_kernel, npix, as_stream(stream), x, y, C, W, H * W, ldy, npix);
+    return check_launch("nchw_to_nhwc_flip");
 }
 extern "C" int up_nhwc_to_nchw_t(const void* x, int ldx, float* y, int N, int C, int H, int W, int dt_in, void* stream) {
     UP_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0 && ldx >= C && UP_DT_OK(dt_in), UP_ERR_INVALID,
@@ -1309,6 +1424,61 @@ extern "C" int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stri
         hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P, Q, sh,
                            sw, make_fastdiv(Q), idx, preds_xy, maxvals);
     return check_launch("heatmap_decode");
+}
+
+// B x J maps of H x W behind three positive element strides: every count and the offset of the last element within int32
+static bool maps_in_int32(int64_t sb, int64_t sj, int64_t sp, int B, int J, int H, int W) {
+    const int64_t lim = INT32_MAX;
+    return (int64_t)B * J <= lim && (int64_t)H * W <= lim && sb <= lim && sj <= lim && sp <= lim && (B - 1) * sb <= lim &&
+           (J - 1) * sj <= lim && ((int64_t)H * W - 1) * sp <= lim && (B - 1) * sb + (J - 1) * sj + ((int64_t)H * W - 1) * sp <= lim;
+}
+
+extern "C" int up_flip_merge(const float* a, const float* f, int64_t in_stride_b, int64_t in_stride_j, int64_t in_stride_p, int B,
+                             int J, int H, int W, const int32_t* perm_host, float* out, int64_t out_stride_b, int64_t out_stride_j,
+                             int64_t out_stride_p, void* stream) {
+    UP_REQUIRE(a && f && perm_host && out, UP_ERR_INVALID, "flip_merge: null argument");
+    UP_REQUIRE(B > 0 && J > 0 && H > 0 && W > 0 && in_stride_b > 0 && in_stride_j > 0 && in_stride_p > 0 && out_stride_b > 0 &&
+                   out_stride_j > 0 && out_stride_p > 0,
+               UP_ERR_INVALID, "flip_merge: %d x %d maps of %d x %d, strides %lld / %lld / %lld -> %lld / %lld / %lld", B, J, H, W,
+               (long long)in_stride_b, (long long)in_stride_j, (long long)in_stride_p, (long long)out_stride_b,
+               (long long)out_stride_j, (long long)out_stride_p);
+    UP_REQUIRE(J <= 256, UP_ERR_UNSUPPORTED, "flip_merge: %d channels (the permutation travels as 256 bytes of kernel arguments)", J);
+    FlipPerm perm;
+    memset(&perm, 0, sizeof(perm));
+    for (int j = 0; j < J; ++j) {
+        UP_REQUIRE(perm_host[j] >= 0 && perm_host[j] < J, UP_ERR_INVALID, "flip_merge: perm[%d] = %d outside 0..%d", j,
+                   (int)perm_host[j], J - 1);
+        perm.v[j] = (uint8_t)perm_host[j];
+    }
+    UP_REQUIRE(out != f, UP_ERR_INVALID, "flip_merge: out == f (the mirrored reads cross threads)");
+    UP_REQUIRE(out != a || (out_stride_b == in_stride_b && out_stride_j == in_stride_j && out_stride_p == in_stride_p), UP_ERR_INVALID,
+               "flip_merge: out == a needs equal strides");
+    UP_REQUIRE(maps_in_int32(in_stride_b, in_stride_j, in_stride_p, B, J, H, W) &&
+                   maps_in_int32(out_stride_b, out_stride_j, out_stride_p, B, J, H, W),
+               UP_ERR_INVALID, "flip_merge: %d x %d maps of %d x %d: an index beyond the int32 range", B, J, H, W);
+    const int64_t total = (int64_t)B * J * H * W;
+    if (out_stride_j < out_stride_p)
+        UP_LAUNCH_1D(flip_merge_kernel<true>, total, as_stream(stream), a, f, in_stride_b, in_stride_j, in_stride_p, J, H, W, perm,
+                     out, out_stride_b, out_stride_j, out_stride_p, total);
+    else
+        UP_LAUNCH_1D(flip_merge_kernel<false>, total, as_stream(stream), a, f, in_stride_b, in_stride_j, in_stride_p, J, H, W, perm,
+                     out, out_stride_b, out_stride_j, out_stride_p, total);
+    return check_launch("flip_merge");
+}
+
+extern "C" int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W,
+                              int res0, int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals,
+                              void* stream) {
+    UP_REQUIRE(hm && preds_xy && maxvals, UP_ERR_INVALID, "final_preds: null argument");
+    UP_REQUIRE(B > 0 && J > 0 && H > 0 && W > 0 && stride_b > 0 && stride_j > 0 && stride_p > 0 && res0 > 0 && res1 > 0,
+               UP_ERR_INVALID, "final_preds: %d x %d maps of %d x %d, strides %lld / %lld / %lld, res %d, %d", B, J, H, W,
+               (long long)stride_b, (long long)stride_j, (long long)stride_p, res0, res1);
+    UP_REQUIRE(maps_in_int32(stride_b, stride_j, stride_p, B, J, H, W) && (int64_t)B * J * 2 <= INT32_MAX, UP_ERR_INVALID,
+               "final_preds: %d x %d maps of %d x %d: an index beyond the int32 range", B, J, H, W);
+    const int maps = B * J;
+    hipLaunchKernelGGL(final_preds_kernel, dim3(cdiv(maps, 4)), dim3(256), 0, as_stream(stream), hm, stride_b, stride_j, stride_p,
+                       maps, J, H, W, res0, res1, inv, preds_xy, coords_xy, maxvals);
+    return check_launch("final_preds");
 }
 
 extern "C" int up_make_heatmaps(const double* kpt_xy, int B, int K, int H, int W, double stride, double sigma,

@@ -1828,6 +1828,78 @@ def heatmap_decode_nhwc(x: torch.Tensor, channels: int, size=None):
     return _decode(x.detach(), (h * w * ld, 1, ld), b, channels, h, w, size)
 
 
+def _perm_array(perm, channels: int):
+    import ctypes
+    perm = [int(p) for p in perm]
+    if len(perm) != channels:
+        raise ValueError(f"a permutation of {len(perm)} channels for maps with {channels}")
+    return (ctypes.c_int32 * channels)(*perm)
+
+
+def flip_merge(a: torch.Tensor, f: torch.Tensor, perm, out: torch.Tensor = None):
+    """The flip test's combine step on NCHW maps (``up_flip_merge``): ``0.5 * (a + f[:, perm].flip(3))`` — `a` the maps of the
+    images as given, `f` the maps of the mirrored images, `perm` from ``protocol.flip_perm``.  The mean, not pytorch-pose's sum:
+    the argmax is the same and the values stay heat-maps.  `out` may be `a`; it must not be `f`."""
+    _dev_ok(a, f, out)
+    if a.dtype != torch.float32 or f.dtype != torch.float32 or a.dim() != 4 or a.shape != f.shape or a.device != f.device:
+        raise ValueError(f"flip_merge: two float32 (B,J,H,W) tensors on one device, got {tuple(a.shape)} {a.dtype} and "
+                         f"{tuple(f.shape)} {f.dtype}")
+    a, f = _dense(a.detach()), _dense(f.detach())
+    b, j, h, w = a.shape
+    if out is None:
+        out = torch.empty_like(a)
+    elif out.shape != a.shape or out.dtype != torch.float32 or out.device != a.device or not out.is_contiguous():
+        raise ValueError(f"flip_merge: `out` is {tuple(out.shape)} {out.dtype}, a contiguous float32 {tuple(a.shape)} expected")
+    s = (j * h * w, h * w, 1)
+    _C.check(_C.lib().up_flip_merge(a.data_ptr(), f.data_ptr(), *s, b, j, h, w, _perm_array(perm, j), out.data_ptr(), *s,
+                                    _stream(a)), "flip_merge")
+    return out
+
+
+def _final_preds(t, strides, b, j, h, w, center, scale, res, return_coords):
+    from . import protocol
+    res = [w, h] if res is None else protocol._res(res)
+    inv = None
+    if center is not None:
+        inv = torch.from_numpy(protocol.inverse_maps(center, scale, res))
+        if tuple(inv.shape) != (b, 2, 3):
+            raise ValueError(f"final_preds: {inv.shape[0]} centres for {b} samples")
+        inv = inv.to(t.device)
+    preds = torch.empty((b, j, 2), dtype=torch.float32, device=t.device)
+    coords = torch.empty((b, j, 2), dtype=torch.float32, device=t.device) if return_coords else None
+    mx = torch.empty((b, j, 1), dtype=torch.float32, device=t.device)
+    _C.check(_C.lib().up_final_preds(t.data_ptr(), *strides, b, j, h, w, int(res[0]), int(res[1]), _ptr(inv), preds.data_ptr(),
+                                     _ptr(coords), mx.data_ptr(), _stream(t)), "final_preds")
+    return (preds, coords, mx) if return_coords else preds
+
+
+def final_preds(output: torch.Tensor, center=None, scale=None, res=None, return_coords: bool = False):
+    """``final_preds`` of pytorch-pose (utils/extra_utils/evaluation.py:75-97) on the device, one launch (``up_final_preds``):
+    NCHW score maps (B, J, H, W) -> preds (B, J, 2) float32 in source-image pixels: the 1-based peak, a quarter pixel towards the
+    larger neighbour, + 0.5, back through the inverse of the centre / scale crop (``protocol.inverse_maps``, made on the host
+    from `center` (B, 2) and `scale` (B,) as the loader gives them), truncated to integers.  ``center=None``: the heat-map
+    coordinates themselves.  `res` = [W, H] by default; res[0] bounds x and res[1] bounds y as in the reference, which is the
+    opposite of get_transform's order.  return_coords: (preds, coords (B,J,2) before the way back, maxvals (B,J,1))."""
+    _dev_ok(output)
+    if output.dtype != torch.float32 or output.dim() != 4:
+        raise TypeError(f"final_preds: float32 (B,J,H,W) score maps, got {tuple(output.shape)} {output.dtype}")
+    hm = _dense(output.detach())
+    b, j, h, w = hm.shape
+    return _final_preds(hm, (j * h * w, h * w, 1), b, j, h, w, center, scale, res, return_coords)
+
+
+def final_preds_nhwc(x: torch.Tensor, channels: int, center=None, scale=None, res=None, return_coords: bool = False):
+    """``final_preds`` of the first `channels` channels of an NHWC activation (B, h, w, ld) as a convolution leaves it."""
+    _dev_ok(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"final_preds_nhwc: float32 score maps, got {x.dtype}")
+    b, h, w, _ = x.shape
+    ld = _nhwc_ok(x)
+    if not 0 < channels <= x.shape[3]:
+        raise ValueError(f"final_preds_nhwc: {channels} channels of a tensor with {x.shape[3]}")
+    return _final_preds(x.detach(), (h * w * ld, 1, ld), b, channels, h, w, center, scale, res, return_coords)
+
+
 def _as_f64(a, dev):
     t = torch.as_tensor(a, dtype=torch.float64).contiguous()
     t = t.to(dev) if dev is not None else t

@@ -13,6 +13,7 @@ and returns the heat-maps (the two slices of ``unipose(bbox=True)`` when the mod
     heat = plan(images)                      # equal bits to checkpoint.load_folded(...)(images)
     preds, maxvals, idx = plan.keypoints(images)     # equal bits to ops.heatmap_argmax(heat), without the NCHW heat-maps
     kpts, count, status = plan.persons(images, "MPII")        # bbox=True models: ops.persons_decode of the maps, without them
+    preds, coords, maxvals = plan.final_preds(images, center, scale, flip=True, dataset="MPII")   # flip test + pytorch-pose's final_preds
 
 A model built with ``stride != 8`` (the reference's full-resolution mode, model/unipose.py:31-32) gives the heat-maps up-sampled
 to the input size, as the module does; ``keypoints`` then decodes on that grid without ever writing the up-sampled maps
@@ -181,6 +182,72 @@ class UniPosePlan:
         _C.check(_C.lib().up_unipose_persons(self._plan, x.data_ptr(), f, 1, 14, max_persons, count.data_ptr(), status.data_ptr(),
                                              kpts.data_ptr(), ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_persons")
         return kpts, count, status
+
+    def _perm(self, dataset, pairs):
+        from . import ops, protocol
+        return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, self.bbox, pairs), self.out_channels)
+
+    def _flip_ws(self):
+        """the flip test keeps the first pass's heat-maps while the trunk runs again: a larger workspace, made at the first call"""
+        need = max(_C.lib().up_unipose_plan_flip_workspace(self._plan), 256) + 256
+        if self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def flip_heatmaps(self, x: torch.Tensor, dataset: str = None, pairs=None, out: torch.Tensor = None):
+        """The flip test in one call (``up_unipose_flip_forward``): the network on `x` and on the mirrored `x`, the second maps
+        mirrored back with left / right channels exchanged (``protocol.flip_perm(dataset, num_classes, bbox, pairs)``), and the
+        mean of the two — equal bits to ``ops.flip_merge(maps(x), maps(x.flip(3)), perm)``.  Returns ONE (B, out_channels, h, w)
+        tensor on the maps' own grid ceil(H/8) x ceil(W/8), also for a model with ``stride != 8`` and with the box head."""
+        x = self._input(x)
+        perm = self._perm(dataset, pairs)
+        shape = (self.batch, self.out_channels, self.map_height, self.map_width)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            _check_out("UniPosePlan.flip_heatmaps", "out", out, shape, self.device)
+        ws, nbytes = self._flip_ws()
+        _C.check(_C.lib().up_unipose_flip_forward(self._plan, x.data_ptr(), perm, out.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_flip_forward")
+        return out
+
+    def final_preds(self, x: torch.Tensor, center=None, scale=None, res=None, flip: bool = False, dataset: str = None, pairs=None,
+                    out=None):
+        """``ops.final_preds`` of the forward's maps without writing them (``up_unipose_final_preds``): (preds (B, C, 2) in
+        source-image pixels, coords (B, C, 2) on the heat-map grid, maxvals (B, C, 1)), float32, for all C output channels, read
+        straight from the NHWC output of the last convolution.  `center` (B, 2) / `scale` (B,) as the loader gives them, `res`
+        = [W, H] of the maps by default; ``center=None``: preds = coords.  flip: the flip test first (``flip_heatmaps``), with
+        `dataset` / `pairs` naming the left / right channels.  Always on the maps' own grid ceil(H/8) x ceil(W/8), also for a
+        model with ``stride != 8``.  `out`: a (preds, coords, maxvals) triple to write into."""
+        from . import protocol
+        x = self._input(x)
+        perm = self._perm(dataset, pairs) if flip else None
+        res = [self.map_width, self.map_height] if res is None else protocol._res(res)
+        inv = None
+        if center is not None:
+            inv = torch.from_numpy(protocol.inverse_maps(center, scale, res))
+            if tuple(inv.shape) != (self.batch, 2, 3):
+                raise ValueError(f"UniPosePlan.final_preds: {inv.shape[0]} centres for a batch of {self.batch}")
+            inv = inv.to(self.device)
+        B, C_ = self.batch, self.out_channels
+        shapes = ((B, C_, 2), (B, C_, 2), (B, C_, 1))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        elif len(out) != 3:
+            raise ValueError("UniPosePlan.final_preds: `out` is a (preds, coords, maxvals) triple")
+        preds, coords, maxvals = (_check_out("UniPosePlan.final_preds", n, t, s, self.device)
+                                  for n, t, s in zip(("preds", "coords", "maxvals"), out, shapes))
+        if flip:
+            ws, nbytes = self._flip_ws()
+        else:
+            off = (-self.workspace.data_ptr()) % 256
+            ws, nbytes = self.workspace.data_ptr() + off, self.workspace.numel() - off
+        _C.check(_C.lib().up_unipose_final_preds(self._plan, x.data_ptr(), perm, None if inv is None else inv.data_ptr(), int(res[0]),
+                                                 int(res[1]), preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
+                                                 self._stream()), "unipose_final_preds")
+        return preds, coords, maxvals
 
     def close(self):
         if self._plan:

@@ -294,7 +294,11 @@ class Trainer(_TrainerBase):
     and ``test`` read the joint maps only.
 
     ``args.augment`` (default off): the TRAINING batcher augments on the device (``augment.Augmenter`` seeded per rank,
-    ``ops.augment_image``); validation and ``test`` never do."""
+    ``ops.augment_image``); validation and ``test`` never do.
+
+    ``args.flip_test`` (default off): validation runs the flip test of the evaluation protocol (utils/extra_utils): the model
+    on the batch and on the mirrored batch, ``ops.flip_merge`` with ``protocol.flip_perm`` of the dataset (box channels
+    included); the loss and ``ops.accuracy`` read the merged maps."""
     batch_size = 8
     sigma = 3
 
@@ -317,17 +321,31 @@ class Trainer(_TrainerBase):
         self.train_batcher = DeviceBatcher(dev, self.stride, self.sigma, bbox=self.bbox, augment=aug) if aug is not None else self.batcher
         model = unipose(args.dataset, num_classes=self.numClasses, backbone="resnet", output_stride=16, sync_bn=True,
                         freeze_bn=False, stride=self.stride, bbox=self.bbox)
+        self.flip_test = bool(getattr(args, "flip_test", False))
+        if self.flip_test:
+            from . import protocol
+            self.flip_perm = protocol.flip_perm(args.dataset, self.numClasses, self.bbox)
         self._setup(model, args, dev)
 
     def _load_pretrained(self, path):
         return checkpoint.load_checkpoint(self.model, path)            # unipose.py:78-90
 
+    def _flip_forward(self, x):
+        """the flip test: the maps of x merged with the mirrored-back maps of the mirrored x (joint maps, or (joint, box) maps)"""
+        a, f = self.model(x), self.model(torch.flip(x, [3]))
+        if not self.bbox:
+            return ops.flip_merge(a, f, self.flip_perm)
+        n = self.numClasses + 1
+        merged = ops.flip_merge(torch.cat(a, 1), torch.cat(f, 1), self.flip_perm)
+        return merged[:, :n], merged[:, n:]
+
     def _forward_loss(self, batch):
         """batch of the batcher -> (joint maps, loss); with the box head the loss is the sum of the two criterion calls"""
+        flip = self.flip_test and not self.model.training
         if not self.bbox:
-            heat = self.model(batch[0])
+            heat = self._flip_forward(batch[0]) if flip else self.model(batch[0])
             return heat, self.criterion(heat, batch[1])
-        heat, box = self.model(batch[0])
+        heat, box = self._flip_forward(batch[0]) if flip else self.model(batch[0])
         return heat, self.criterion(heat, batch[1]) + self.criterion(box, batch[3])
 
     def training(self, epoch):
