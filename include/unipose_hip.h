@@ -419,6 +419,24 @@ int up_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int N, int H,
 int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream);
 int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q, void* stream);
 int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream);
+/* The clip kernels of the video plan's evaluation entries (ABI 10 additions).  Each is its non-clip / non-mirrored neighbour with
+ * the frame-major order (and the mirror) folded in, equal bits to the composition:
+ *   up_clip_nchw_to_nhwc_flip    y[f, h, w, c] = x[b, t, c, h, W-1-w] for f = t * B + b, pad channels zero: up_clip_nchw_to_nhwc of
+ *                                the mirrored clip.
+ *   up_clip_avgpool9s8_flip_fwd  up_clip_avgpool9s8_fwd of the mirrored centre maps, read in place.  The window of output column q is
+ *                                that of the MIRRORED map (the padding sits on one side, so it is not the mirror of the window of
+ *                                column Q-1-q), summed over ascending columns of the mirrored map, the same divisor: equal bits to
+ *                                pooling cm.flip(-1).  Only channel coff is written.
+ *   up_clip_heatmap_decode       up_heatmap_decode for T * B frame-major images: image f = t * B + b is read at hm + f * stride_b,
+ *                                its J results go to row b * T + t of idx (B,T,J) (may be NULL), preds_xy (B,T,J,2), maxvals (B,T,J).
+ *                                The same arithmetic, LDS staging and NaN / tie rules; T == 1 is up_heatmap_decode.
+ *   up_clip_final_preds          up_final_preds with the same reordering; inv (B,T,2,3) float64 batch-major, one crop per frame (may
+ *                                be NULL, like coords_xy).
+ * UP_ERR_INVALID (nothing launched): a null pointer, a size or a stride <= 0, P, Q not the pooled size, an offset beyond int32, and
+ * what the neighbours refuse. */
+int up_clip_nchw_to_nhwc_flip(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream);
+int up_clip_avgpool9s8_flip_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q, void* stream);
+/* (up_clip_heatmap_decode / up_clip_final_preds are declared with their neighbours below) */
 /* nn.Dropout (wasp.py:63, decoder.py:25,29): keep-mask from a counter hash of (seed, element index)
  * or, when ext_mask != NULL, from the caller (float 0/1) — the injectable-RNG hook used for parity.
  * UP_ERR_INVALID (nothing written): a null x / y / mask, n <= 0, p < 0 or p >= 1, an unknown dtype. */
@@ -485,6 +503,9 @@ int up_heatmap_argmax(const float* hm, int B, int J, int H, int W,
  * not a reference use), P * Q or the offset of the last element beyond the int32 range. */
 int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W,
                       int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream);
+/* ... of T * B frame-major images into batch-major results (see the clip kernels above) */
+int up_clip_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int T, int J, int H, int W,
+                           int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream);
 
 /* ---- the evaluation protocol around the forward: flip test and final_preds (ABI 10 additions) ----
  * What published PCKh numbers of this family of networks add to get_max_preds (utils/extra_utils, vendored from pytorch-pose):
@@ -524,6 +545,8 @@ int up_flip_merge(const float* a, const float* f, int64_t in_stride_b, int64_t i
                   int64_t out_stride_p, void* stream);
 int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W, int res0,
                    int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals, void* stream);
+int up_clip_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int T, int J, int H, int W,
+                        int res0, int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals, void* stream);
 
 /* ---- training targets and input normalisation (the step BEFORE the path) ----
  * up_make_heatmaps: lsp_lspet_data.py:224-236 / mpii_data.py:165-175.  kpt_xy (B,K,2) float64 pixel coordinates of the
@@ -732,9 +755,39 @@ int up_unipose_final_preds(up_unipose_plan* plan, const float* x_nchw, const int
  * Convolution names are the reference's state_dict prefixes: the trunk's (wasp.conv2 twice; the video WASP's
  * wasp.global_avg_pool.1 has no bias), lstm_0.conv_{g,i,o}_lstm, lstm.conv_{g,i,o,f}{x,h}_lstm and conv1 .. conv5.  The plan
  * stacks the gate weights itself once all parts of a cell are set; a forward call while any is unset fails ("never set").
- * Both forms return heat-maps, on the h x w grid only (the reference's video model stores `stride` and never up-samples).  For
- * key points, decode them with up_heatmap_decode on the NCHW output: T * B * (K+1) maps in one launch, stride_b = (K+1) * h * w,
- * stride_j = h * w, stride_p = 1, and P x Q = h x w or an up-sampled grid. */
+ * Both forms return heat-maps, on the h x w grid only (the reference's video model stores `stride` and never up-samples).
+ *
+ * The evaluation entries run the same convolution launches over the same weight store and read the NHWC output of conv5 directly;
+ * the plan keeps a clip frame-major inside, results are batch-major (B, T, ...):
+ *   up_unipose_lstm_clip_keypoints    the clip program up to conv5, then up_clip_heatmap_decode: idx (B,T,K+1) (may be NULL),
+ *                                     preds_xy (B,T,K+1,2), maxvals (B,T,K+1) on the out_h x out_w grid, which is h x w or the
+ *                                     input's H x W (anything else: UP_ERR_INVALID); cell_last / hide_last as up_unipose_lstm_clip
+ *                                     (may be NULL).  No NCHW heat tensor is written.
+ *   up_unipose_lstm_clip_flip         the flip test, this project's extension (the reference's video drivers run none): the whole clip
+ *                                     program on the clip and again on the mirrored clip (up_clip_nchw_to_nhwc_flip; the mirrored centre
+ *                                     maps pooled from the mirrored side, up_clip_avgpool9s8_flip_fwd), each pass with its own
+ *                                     recurrent state, every convolution launch one that up_unipose_lstm_clip makes; the first pass's
+ *                                     heat-maps stay alive through the second; then up_flip_merge in place with perm_host (K+1 int32 on
+ *                                     the host) and up_clip_nhwc_to_nchw into heat (B, T, K+1, h, w).  Equal bits to merging
+ *                                     up_unipose_lstm_clip of the clip and of the mirrored clip frame by frame.  No state is
+ *                                     returned: there are two.
+ *   up_unipose_lstm_clip_final_preds  the same merged in place, then up_clip_final_preds: preds_xy, coords_xy (may be NULL)
+ *                                     (B,T,K+1,2), maxvals (B,T,K+1); inv (device, (B,T,2,3) float64, one crop per frame) may be NULL.
+ *                                     perm_host == NULL: one pass, no flip test.
+ *   up_unipose_lstm_stream_keypoints  one frame in, joints out, for a caller that feeds a camera: the step program with hide and cell
+ *                                     kept in `state`, a caller-owned, opaque, 256-byte aligned device buffer of
+ *                                     up_unipose_lstm_plan_state_bytes() bytes (the plan's own NHWC (B, h, w, rup4(K+2)), twice), then
+ *                                     up_heatmap_decode on the out_h x out_w grid: idx (B,K+1) (may be NULL), preds_xy (B,K+1,2),
+ *                                     maxvals (B,K+1); heat_nchw (B, K+1, h, w) may be NULL.  first != 0: LSTM_0, nothing is read from
+ *                                     `state`, the new state is written into it; first == 0: the state is copied into the program's
+ *                                     tensors and overwritten with the new one at the end.  Whole padded rows are copied, so the pad
+ *                                     channels stay the zeros the plan wrote.  Several streams may share one plan (and workspace,
+ *                                     calls in stream order), each with its own buffer.  A NULL or misaligned state: UP_ERR_INVALID.
+ * Workspaces: up_unipose_lstm_plan_program_workspace(plan, k) is the need of program k alone, in the order 0 step-first, 1 step-next,
+ * 2 clip, 3 clip_keypoints, 4 clip_flip, 5 clip_final_preds with and 6 without the flip test, 7 stream-first, 8 stream-next, 0 for any
+ * other k.  up_unipose_lstm_plan_workspace() is the largest of 0..3 and 6..8 (step and clip ask for exactly that, as before),
+ * up_unipose_lstm_plan_flip_workspace() of 4 and 5; an evaluation entry asks for its own program's need.  Unset weights, a too-small
+ * workspace, a perm entry outside 0..K, res <= 0 and a null required pointer are refused before anything is launched. */
 typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
 typedef struct {
     int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */
@@ -753,6 +806,20 @@ int up_unipose_lstm_step(up_unipose_lstm_plan* plan, const float* x_nchw, const 
                          size_t workspace_bytes, void* stream);
 int up_unipose_lstm_clip(up_unipose_lstm_plan* plan, const float* x, const float* center, float* heat, float* cell_last,
                          float* hide_last, void* workspace, size_t workspace_bytes, void* stream);
+size_t up_unipose_lstm_plan_flip_workspace(const up_unipose_lstm_plan* plan);
+size_t up_unipose_lstm_plan_program_workspace(const up_unipose_lstm_plan* plan, int program);
+size_t up_unipose_lstm_plan_state_bytes(const up_unipose_lstm_plan* plan);
+int up_unipose_lstm_clip_keypoints(up_unipose_lstm_plan* plan, const float* x, const float* center, int out_h, int out_w, int32_t* idx,
+                                   float* preds_xy, float* maxvals, float* cell_last, float* hide_last, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int up_unipose_lstm_clip_flip(up_unipose_lstm_plan* plan, const float* x, const float* center, const int32_t* perm_host, float* heat,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* plan, const float* x, const float* center, const int32_t* perm_host,
+                                     const double* inv, int res0, int res1, float* preds_xy, float* coords_xy, float* maxvals,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* plan, const float* x_nchw, const float* center_nchw, void* state, int first,
+                                     int out_h, int out_w, int32_t* idx, float* preds_xy, float* maxvals, float* heat_nchw,
+                                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg; no reference counterpart) ----
  * Between begin/end every MFMA convolution launch is bracketed by two hipEvents on its stream;

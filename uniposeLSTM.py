@@ -6,6 +6,17 @@ dataset Penn_Action and five-frame clips are fixed like there (:284-289); the lo
 import argparse
 
 
+def parse_pairs(text):
+    """ "1,2;3,4" -> [[1, 2], [3, 4]] """
+    try:
+        pairs = [[int(v) for v in pair.split(",")] for pair in text.split(";") if pair.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"joint pairs like 1,2;3,4 expected, got {text!r}")
+    if not pairs or any(len(pair) != 2 for pair in pairs):
+        raise argparse.ArgumentTypeError(f"joint pairs like 1,2;3,4 expected, got {text!r}")
+    return pairs
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--pretrained", default=None, type=str, dest="pretrained")
@@ -23,6 +34,11 @@ def parse_args(argv=None):
     p.add_argument("--val_batches", default=1, type=int)
     p.add_argument("--augment", action="store_true",
                    help="augment the training batches on the device (resize, rotate, crop, mirror as utils/Mytransforms.py; default off)")
+    p.add_argument("--flip-test", dest="flip_test", action="store_true",
+                   help="validate with the flip test: mean of each frame's maps and the mirrored-back maps of the mirrored clip "
+                        "(this project's extension; needs --flip-pairs, the reference has no left / right list for Penn_Action)")
+    p.add_argument("--flip-pairs", dest="flip_pairs", default=None, type=parse_pairs,
+                   help='left / right joint pairs of the flip test, 0-based: "1,2;3,4;..."')
     args = p.parse_args(argv)
     args.dataset = "Penn_Action"
     return args

@@ -182,6 +182,17 @@ SIGNATURES = {
     "up_unipose_lstm_plan_workspace": (_sz, [_p]),
     "up_unipose_lstm_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "up_unipose_lstm_clip": (_i, [_p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "up_clip_nchw_to_nhwc_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_avgpool9s8_flip_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_heatmap_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "up_clip_final_preds": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "up_unipose_lstm_plan_flip_workspace": (_sz, [_p]),
+    "up_unipose_lstm_plan_program_workspace": (_sz, [_p, _i]),
+    "up_unipose_lstm_plan_state_bytes": (_sz, [_p]),
+    "up_unipose_lstm_clip_keypoints": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_lstm_clip_flip": (_i, [_p, _p, _p, C.POINTER(C.c_int32), _p, _p, _sz, _p]),
+    "up_unipose_lstm_clip_final_preds": (_i, [_p, _p, _p, C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_lstm_stream_keypoints": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "up_profile_variants": (_i, []),
     "up_profile_variant_name": (C.c_char_p, [_i]),
     "up_profile_begin": (_i, []),

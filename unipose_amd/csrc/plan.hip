@@ -77,7 +77,10 @@ enum Kind {
     // the evaluation protocol (ABI 10 additions): the mirrored layout pass, the flip test's combine step, final_preds from NHWC
     TO_NHWC_FLIP, MERGE, FINAL,
     // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
-    POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL
+    POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL,
+    // its evaluation entries (ABI 10 additions): the mirrored clip layout and pooling, decode / final_preds of frame-major maps
+    // into batch-major results, the recurrent state of a stream from and to the caller's buffer
+    CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL, STATE_IN, STATE_OUT
 };
 enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
 struct Op {
@@ -430,21 +433,34 @@ static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
 }
 
 // ---- UniPose-LSTM (model/uniposeLSTM.py:67-138; the drop-in module unipose_amd/uniposeLSTM.py after checkpoint.load_folded) ----
-enum LstmForm { STEP_FIRST, STEP_NEXT, CLIP };
+// STEP_FIRST / STEP_NEXT: the module's per-frame path (batch_frames = False) for iter == 0 (LSTM_0) resp. iter > 0 with the caller's
+// NCHW state; CLIP: its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True).  The evaluation entries run the same
+// launches and end differently: CLIP_KEYPOINTS decodes the NHWC output of conv5 (up_clip_heatmap_decode); CLIP_FLIP runs the whole
+// clip program twice, on the clip and on the mirrored clip (up_clip_nchw_to_nhwc_flip, up_clip_avgpool9s8_flip_fwd), each pass with
+// its own recurrent state, the first pass's heat-maps staying alive through the second, then up_flip_merge in place and the layout
+// pass; CLIP_FLIP_PREDS: the same, then up_clip_final_preds; CLIP_PREDS: one pass, then up_clip_final_preds.  STREAM_FIRST /
+// STREAM_NEXT: the step forms with the recurrent state in the caller's opaque NHWC buffer (whole padded rows copied in and out)
+// and up_heatmap_decode at the end; the NCHW heat-maps are optional.
+enum LstmForm { STEP_FIRST, STEP_NEXT, CLIP, CLIP_KEYPOINTS, CLIP_FLIP, CLIP_FLIP_PREDS, CLIP_PREDS, STREAM_FIRST, STREAM_NEXT, LSTM_FORMS };
 
-// One program of the video plan.  STEP_FIRST / STEP_NEXT: the module's per-frame path (batch_frames = False) for iter == 0 (LSTM_0)
-// resp. iter > 0 with the caller's NCHW state; CLIP: its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True) — the
-// trunk once on the T * B frame-major images, the recurrence frame by frame on rows of frame-major state tensors, the head once on
-// the T * B hidden states.  Stacked gate convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).
-static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) {
-    const int B = c.batch, T = form == CLIP ? c.frames : 1, n = T * B;
+struct LstmPass {
+    Ref y, cells, hides;       // conv5's output and the state tensors, frame-major (T * B, h, w, .)
+    int h = 0, w = 0;
+};
+
+// One pass of a video program up to conv5: the trunk once on the T * B frame-major images (T = 1 in the step and stream forms), the
+// recurrence frame by frame on rows of frame-major state tensors, the head once on the T * B hidden states.  Stacked gate
+// convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).  mirrored: the pass of the flip test.
+static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm form, bool mirrored) {
+    const bool clip = form >= CLIP && form <= CLIP_PREDS, next = form == STEP_NEXT || form == STREAM_NEXT;
+    const int B = c.batch, T = clip ? c.frames : 1, n = T * B;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
     int h = c.height, w = c.width;
     Ref x;
     x.id = p.tensor(n, h, w, 4);
     {
         Op op;
-        op.kind = form == CLIP ? CLIP_TO_NHWC : TO_NHWC;
+        op.kind = !clip ? TO_NHWC : mirrored ? CLIP_TO_NHWC_FLIP : CLIP_TO_NHWC;
         op.out = x;
         op.ext = X;
         op.n = B; op.a = T; op.c = 3;
@@ -462,7 +478,7 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) 
     const int ldz = p.tensors[z.id].c;       // == ldo either way
     {
         Op op;
-        op.kind = form == CLIP ? CLIP_POOL : POOL;
+        op.kind = !clip ? POOL : mirrored ? CLIP_POOL_FLIP : CLIP_POOL;
         op.out = z;
         op.ext = CENTER;
         op.n = B; op.e = T;
@@ -486,21 +502,29 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) 
         Op op;
         op.n = B; op.c = cg;
         op.out = ct; op.res = ht;
-        if (t == 0 && form != STEP_NEXT) {    // LSTM_0 (uniposeLSTM.py:9-24)
+        if (t == 0 && !next) {                // LSTM_0 (uniposeLSTM.py:9-24)
             op.kind = LSTM0;
             op.in = p.conv("lstm_0", zt, B, h, w, ldz, cg, 3 * cg, 3, 1, 1, 1, 0, true);
         } else {                              // LSTM (uniposeLSTM.py:27-64): ONE convolution over cat(z, prev_hide)
             Ref ph, pc;
-            if (form == STEP_NEXT) {          // the caller's NCHW state (unipose._state: ToNHWC, pad channels zero)
+            if (next) {
                 ph.id = p.tensor(B, h, w, ldo);
                 pc.id = p.tensor(B, h, w, ldo);
                 Op in;
-                in.kind = TO_NHWC;
-                in.n = B; in.c = cg;
-                in.out = ph; in.ext = PREV_HIDE;
-                p.push(in);
-                in.out = pc; in.ext = PREV_CELL;
-                p.push(in);
+                if (form == STEP_NEXT) {      // the caller's NCHW state (unipose._state: ToNHWC, pad channels zero)
+                    in.kind = TO_NHWC;
+                    in.n = B; in.c = cg;
+                    in.out = ph; in.ext = PREV_HIDE;
+                    p.push(in);
+                    in.out = pc; in.ext = PREV_CELL;
+                    p.push(in);
+                } else {                      // the caller's state buffer: the plan's own NHWC rows, pad channels as the plan left them
+                    in.kind = STATE_IN;
+                    in.out = ph; in.a = 0;
+                    p.push(in);
+                    in.out = pc; in.a = 1;
+                    p.push(in);
+                }
             } else {
                 ph = hides;
                 pc = cells;
@@ -523,15 +547,65 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) 
     y = p.conv("conv3", y, n, h, w, 128, 128, 128, 11, 1, 5, 1, 1, true);
     y = p.conv("conv4", y, n, h, w, 128, 128, 128, 1, 1, 0, 1, 1, true);
     y = p.conv("conv5", y, n, h, w, 128, 128, hc, 1, 1, 0, 1, 1, true);
+    LstmPass r;
+    r.y = y; r.cells = cells; r.hides = hides;
+    r.h = h; r.w = w;
+    return r;
+}
+
+static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) {
+    const bool clip = form >= CLIP && form <= CLIP_PREDS, stream = form == STREAM_FIRST || form == STREAM_NEXT;
+    const int B = c.batch, T = clip ? c.frames : 1;
+    const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
+    const LstmPass a = lstm_pass(p, c, form, false);
     Op op;
-    op.kind = form == CLIP ? CLIP_TO_NCHW : TO_NCHW;
-    op.in = y;
-    op.ext = HEAT;
-    op.n = B; op.a = T; op.c = hc;
-    p.push(op);
-    Ref cl = cells, hl = hides;                // the state of the last frame
+    if (form == CLIP_FLIP || form == CLIP_FLIP_PREDS) {
+        const LstmPass m = lstm_pass(p, c, form, true);
+        op.kind = MERGE;                       // in place (NHWC): out == a with equal strides; both passes are frame-major
+        op.in = a.y; op.aux = m.y; op.out = a.y;
+        op.n = T * B; op.c = hc;
+        p.push(op);
+    }
+    if (form == CLIP_FLIP_PREDS || form == CLIP_PREDS || form == CLIP_KEYPOINTS) {
+        op = Op();
+        op.kind = form == CLIP_KEYPOINTS ? CLIP_DECODE : CLIP_FINAL;
+        op.in = a.y;
+        op.n = B; op.a = T; op.c = hc;
+        p.push(op);
+    }
+    if (form == CLIP_FLIP_PREDS || form == CLIP_PREDS) {
+        p.layout();
+        return;
+    }
+    const size_t frame = (size_t)B * a.h * a.w;
+    Ref cl = a.cells, hl = a.hides;            // the state of the last frame
     cl.elems += (T - 1) * frame * ldo;
     hl.elems += (T - 1) * frame * ldo;
+    if (stream) {                              // the new state into the caller's buffer, then the joints
+        op = Op();
+        op.kind = STATE_OUT;
+        op.in = hl; op.a = 0;
+        p.push(op);
+        op.in = cl; op.a = 1;
+        p.push(op);
+        op = Op();
+        op.kind = DECODE;
+        op.in = a.y;
+        op.n = B; op.c = hc;
+        p.push(op);
+    }
+    if (form != CLIP_KEYPOINTS) {
+        op = Op();
+        op.kind = clip ? CLIP_TO_NCHW : TO_NCHW;     // TO_NCHW is skipped where the caller passes no tensor (the stream forms' heat)
+        op.in = a.y;
+        op.ext = HEAT;
+        op.n = B; op.a = T; op.c = hc;
+        p.push(op);
+    }
+    if (form == CLIP_FLIP || stream) {         // a flip program has two states and returns none; a stream's state is in its buffer
+        p.layout();
+        return;
+    }
     op = Op();
     op.kind = TO_NCHW;
     op.n = B; op.c = cg;
@@ -563,6 +637,8 @@ struct Io {
     const double* inv = nullptr;
     int res0 = 0, res1 = 0;
     float* coords = nullptr;
+    float* state = nullptr;          // STATE_IN / STATE_OUT: the caller's buffer, hide then cell, state_half elements each
+    size_t state_half = 0;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -655,6 +731,31 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
         case CLIP_TO_NCHW:
             e = up_clip_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.heat, op.n, op.a, op.c, T_(op.in).h, T_(op.in).w, stream);
             break;
+        case CLIP_TO_NHWC_FLIP:
+            e = up_clip_nchw_to_nhwc_flip(io.x, ptr(op.out), op.n, op.a, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            break;
+        case CLIP_POOL_FLIP:
+            e = up_clip_avgpool9s8_flip_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.e, op.a, op.b, T_(op.out).h,
+                                            T_(op.out).w, stream);
+            break;
+        case CLIP_DECODE:
+            e = up_clip_heatmap_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.a, op.c,
+                                       T_(op.in).h, T_(op.in).w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
+            break;
+        case CLIP_FINAL:
+            e = up_clip_final_preds(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.a, op.c,
+                                    T_(op.in).h, T_(op.in).w, io.res0, io.res1, io.inv, io.preds, io.coords, io.maxvals, stream);
+            break;
+        case STATE_IN: {                       // whole padded rows: the pad channels stay the zeros the plan wrote
+            const Tensor& t = T_(op.out);
+            e = up_copy2d(io.state + op.a * io.state_half, t.c, ptr(op.out), t.c, (int64_t)t.n * t.h * t.w, t.c, stream);
+            break;
+        }
+        case STATE_OUT: {
+            const Tensor& t = T_(op.in);
+            e = up_copy2d(ptr(op.in), t.c, io.state + op.a * io.state_half, t.c, (int64_t)t.n * t.h * t.w, t.c, stream);
+            break;
+        }
         }
         if (e) return e;
     }
@@ -887,8 +988,8 @@ extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, 
 }
 
 // ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------
-// Three programs share one weight store: the per-frame step for the first frame (LSTM_0) and for a later one (LSTM over the
-// caller's state), and the whole clip.  Weights are stored once per distinct parameter; the ConvLSTM gate convolutions are set
+// All programs (LstmForm) share one weight store: the per-frame step for the first frame (LSTM_0) and for a later one (LSTM over
+// the caller's state), the whole clip, and the evaluation entries over the same launches.  Weights are stored once per distinct parameter; the ConvLSTM gate convolutions are set
 // part by part under their state_dict names and stacked by the plan (modules.LSTM_0.forward / modules.LSTM.stacked): along the
 // output channels, the x / h parts' input channels padded to rup4, each gate bias the fp32 sum bx + bh.
 namespace up {
@@ -919,10 +1020,12 @@ struct Entry {                 // one listed convolution
 
 struct up_unipose_lstm_plan {
     up_unipose_lstm_config cfg;
-    Plan prog[3];              // STEP_FIRST, STEP_NEXT, CLIP
+    Plan prog[plan::LSTM_FORMS];
     std::vector<plan::Store> stores;
     std::vector<plan::Entry> entries;
-    size_t ws_bytes = 0;
+    size_t ws_bytes = 0;       // the largest of the programs without the flip test
+    size_t flip_ws_bytes = 0;  // the largest of CLIP_FLIP and CLIP_FLIP_PREDS
+    size_t state_half = 0;     // elements of one (B, h, w, rup4(K + 2)) state tensor in a stream's buffer, a multiple of 64
 };
 
 extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** out) {
@@ -942,9 +1045,15 @@ extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up
     up_unipose_lstm_plan* pl = new (std::nothrow) up_unipose_lstm_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_lstm_plan_create: out of host memory");
     pl->cfg = *cfg;
-    for (int f = 0; f < 3; ++f) {
+    for (int f = 0; f < plan::LSTM_FORMS; ++f) {
         plan::build_lstm(pl->prog[f], pl->cfg, static_cast<plan::LstmForm>(f));
-        pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
+        size_t& need = f == plan::CLIP_FLIP || f == plan::CLIP_FLIP_PREDS ? pl->flip_ws_bytes : pl->ws_bytes;
+        need = std::max(need, pl->prog[f].ws_bytes);
+    }
+    {   // the hidden state STATE_OUT copies: its tensor's padded size
+        const Plan& sp = pl->prog[plan::STREAM_FIRST];
+        for (const plan::Op& op : sp.ops)
+            if (op.kind == plan::STATE_OUT) pl->state_half = sp.tensors[op.in.id].bytes / sizeof(float);
     }
     // the weight store: every distinct name of the three programs
     auto store_of = [&](const std::string& name) {
@@ -1073,11 +1182,22 @@ extern "C" int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* pl, int i, co
 
 extern "C" size_t up_unipose_lstm_plan_workspace(const up_unipose_lstm_plan* pl) { return pl ? pl->ws_bytes : 0; }
 
-static int lstm_ready(const up_unipose_lstm_plan* pl, const void* workspace, size_t ws_bytes, const char* what) {
+extern "C" size_t up_unipose_lstm_plan_flip_workspace(const up_unipose_lstm_plan* pl) { return pl ? pl->flip_ws_bytes : 0; }
+
+extern "C" size_t up_unipose_lstm_plan_program_workspace(const up_unipose_lstm_plan* pl, int program) {
+    return pl && program >= 0 && program < plan::LSTM_FORMS ? pl->prog[program].ws_bytes : 0;
+}
+
+extern "C" size_t up_unipose_lstm_plan_state_bytes(const up_unipose_lstm_plan* pl) {
+    return pl ? 2 * pl->state_half * sizeof(float) : 0;
+}
+
+// `need`: up_unipose_lstm_plan_workspace() for step and clip (as ever), the program's own for the evaluation entries
+static int lstm_ready(const up_unipose_lstm_plan* pl, size_t need, const void* workspace, size_t ws_bytes, const char* what) {
     for (const plan::Entry& e : pl->entries)
         UP_REQUIRE(e.set, UP_ERR_INVALID, "%s: weights of %s were never set (up_unipose_lstm_plan_set_conv)", what, e.name.c_str());
-    UP_REQUIRE(ws_bytes >= pl->ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_WORKSPACE,
-               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, pl->ws_bytes, ws_bytes);
+    UP_REQUIRE(ws_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_WORKSPACE,
+               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, need, ws_bytes);
     return UP_OK;
 }
 
@@ -1088,7 +1208,7 @@ extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nch
                "unipose_lstm_step: null argument");
     UP_REQUIRE((prev_hide == nullptr) == (prev_cell == nullptr), UP_ERR_INVALID,
                "unipose_lstm_step: prev_hide and prev_cell are both given (a later frame) or both NULL (the first frame)");
-    if (int e = lstm_ready(pl, workspace, ws_bytes, "unipose_lstm_step")) return e;
+    if (int e = lstm_ready(pl, pl->ws_bytes, workspace, ws_bytes, "unipose_lstm_step")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.center = center_nchw;
@@ -1104,7 +1224,7 @@ extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nch
 extern "C" int up_unipose_lstm_clip(up_unipose_lstm_plan* pl, const float* x, const float* center, float* heat, float* cell_last,
                                     float* hide_last, void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x && center && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip: null argument");
-    if (int e = lstm_ready(pl, workspace, ws_bytes, "unipose_lstm_clip")) return e;
+    if (int e = lstm_ready(pl, pl->ws_bytes, workspace, ws_bytes, "unipose_lstm_clip")) return e;
     plan::Io io;
     io.x = x;
     io.center = center;
@@ -1112,4 +1232,100 @@ extern "C" int up_unipose_lstm_clip(up_unipose_lstm_plan* pl, const float* x, co
     io.cell = cell_last;
     io.hide = hide_last;
     return plan::run(pl->prog[plan::CLIP], io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip");
+}
+
+// ---- the evaluation entries of the video plan (ABI 10 additions) ---------------------------------------------------------------
+extern "C" int up_unipose_lstm_clip_keypoints(up_unipose_lstm_plan* pl, const float* x, const float* center, int out_h, int out_w,
+                                              int32_t* idx, float* preds_xy, float* maxvals, float* cell_last, float* hide_last,
+                                              void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x && center && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_clip_keypoints: null argument");
+    const int h = (pl->cfg.height - 1) / 8 + 1, w = (pl->cfg.width - 1) / 8 + 1;
+    UP_REQUIRE((out_h == h && out_w == w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
+               "unipose_lstm_clip_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h,
+               out_w, h, w, pl->cfg.height, pl->cfg.width);
+    const Plan& prog = pl->prog[plan::CLIP_KEYPOINTS];
+    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_keypoints")) return e;
+    plan::Io io;
+    io.x = x;
+    io.center = center;
+    io.dec_h = out_h;
+    io.dec_w = out_w;
+    io.idx = idx;
+    io.preds = preds_xy;
+    io.maxvals = maxvals;
+    io.cell = cell_last;
+    io.hide = hide_last;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_keypoints");
+}
+
+// the channel permutation of a flip-test call: refused here, before the first launch of the program (like perm_ok)
+static int lstm_perm_ok(const up_unipose_lstm_plan* pl, const int32_t* perm, const char* what) {
+    const int C = pl->cfg.num_classes + 1;
+    UP_REQUIRE(C <= 256, UP_ERR_UNSUPPORTED, "%s: %d heat-map channels (up_flip_merge takes up to 256)", what, C);
+    for (int j = 0; j < C; ++j)
+        UP_REQUIRE(perm[j] >= 0 && perm[j] < C, UP_ERR_INVALID, "%s: perm[%d] = %d outside 0..%d", what, j, (int)perm[j], C - 1);
+    return UP_OK;
+}
+
+extern "C" int up_unipose_lstm_clip_flip(up_unipose_lstm_plan* pl, const float* x, const float* center, const int32_t* perm_host,
+                                         float* heat, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x && center && perm_host && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip_flip: null argument");
+    if (int e = lstm_perm_ok(pl, perm_host, "unipose_lstm_clip_flip")) return e;
+    const Plan& prog = pl->prog[plan::CLIP_FLIP];
+    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_flip")) return e;
+    plan::Io io;
+    io.x = x;
+    io.center = center;
+    io.perm = perm_host;
+    io.heat = heat;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_flip");
+}
+
+extern "C" int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* pl, const float* x, const float* center, const int32_t* perm_host,
+                                                const double* inv, int res0, int res1, float* preds_xy, float* coords_xy,
+                                                float* maxvals, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x && center && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_clip_final_preds: null argument");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_lstm_clip_final_preds: res %d, %d", res0, res1);
+    if (perm_host)
+        if (int e = lstm_perm_ok(pl, perm_host, "unipose_lstm_clip_final_preds")) return e;
+    const Plan& prog = pl->prog[perm_host ? plan::CLIP_FLIP_PREDS : plan::CLIP_PREDS];
+    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_final_preds")) return e;
+    plan::Io io;
+    io.x = x;
+    io.center = center;
+    io.perm = perm_host;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_final_preds");
+}
+
+extern "C" int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* pl, const float* x_nchw, const float* center_nchw, void* state,
+                                                int first, int out_h, int out_w, int32_t* idx, float* preds_xy, float* maxvals,
+                                                float* heat_nchw, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && x_nchw && center_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID,
+               "unipose_lstm_stream_keypoints: null argument");
+    UP_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 255) == 0, UP_ERR_INVALID,
+               "unipose_lstm_stream_keypoints: a 256-byte aligned state buffer of up_unipose_lstm_plan_state_bytes() bytes is needed");
+    const int h = (pl->cfg.height - 1) / 8 + 1, w = (pl->cfg.width - 1) / 8 + 1;
+    UP_REQUIRE((out_h == h && out_w == w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
+               "unipose_lstm_stream_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h,
+               out_w, h, w, pl->cfg.height, pl->cfg.width);
+    const Plan& prog = pl->prog[first ? plan::STREAM_FIRST : plan::STREAM_NEXT];
+    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_stream_keypoints")) return e;
+    plan::Io io;
+    io.x = x_nchw;
+    io.center = center_nchw;
+    io.state = static_cast<float*>(state);
+    io.state_half = pl->state_half;
+    io.dec_h = out_h;
+    io.dec_w = out_w;
+    io.idx = idx;
+    io.preds = preds_xy;
+    io.maxvals = maxvals;
+    io.heat = heat_nchw;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_stream_keypoints");
 }

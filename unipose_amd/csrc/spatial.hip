@@ -50,11 +50,17 @@ __device__ __forceinline__ int64_t clip_image(int64_t f, int B, int T) {      //
     const int64_t t = f / B;
     return (f - t * B) * T + t;
 }
-__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_kernel(const float* x, float* y, int B, int T, int C, int HW, int ld,
+// FLIP: the mirror folded in (the flip test of the video plan): the NHWC pixel (h, w) takes the NCHW pixel (h, W - 1 - w)
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_kernel(const float* x, float* y, int B, int T, int C, int W, int HW, int ld,
                                                                 int64_t npix) {
     UP_GRID_STRIDE(i, npix) {
         const int64_t f = i / HW;
-        const int hw = (int)(i - f * HW);
+        int hw = (int)(i - f * HW);
+        if (FLIP) {
+            const int h = hw / W;
+            hw = h * W + (W - 1 - (hw - h * W));
+        }
         const float* src = x + clip_image(f, B, T) * C * HW + hw;
         float* dst = y + i * ld;
         for (int c = 0; c < ld; c += 4)
@@ -364,6 +370,9 @@ __global__ void __launch_bounds__(256) gap_bwd_kernel(const T* dy, T* dx, int ld
 
 // ---- AvgPool2d(9, 8, 1), count_include_pad -----------------------------------------------------
 // output pixel (p, q) of the H x W plane `x`: the arithmetic of both launches below (a clip's centre maps pool to the same bits)
+// FLIP: ... of the MIRRORED plane, m[h][w] = x[h][W - 1 - w], read in place: the window and the divisor are those of column q of
+// m (the padding sits on one side, so this is not the window of column Q - 1 - q of x), and the sum runs over ascending w of m
+template <bool FLIP = false>
 __device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int p, int q) {
     int hs = p * 8 - 1, ws = q * 8 - 1;
     int he = min(hs + 9, H + 1), we = min(ws + 9, W + 1);
@@ -374,7 +383,7 @@ __device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int
     we = min(we, W);
     float s = 0.f;
     for (int h = hs; h < he; ++h)
-        for (int w = ws; w < we; ++w) s += x[h * W + w];
+        for (int w = ws; w < we; ++w) s += x[h * W + (FLIP ? W - 1 - w : w)];
     return s / div;
 }
 __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int H, int W,
@@ -388,6 +397,7 @@ __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* 
     }
 }
 // ... of a clip's (B, T, 1, H, W) centre maps into channel coff of the frame-major (T * B, P, Q, ldy) hand-over tensor
+template <bool FLIP>
 __global__ void __launch_bounds__(256) clip_avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int B, int T, int H,
                                                               int W, int P, int Q, int64_t total) {
     UP_GRID_STRIDE(i, total) {
@@ -395,7 +405,7 @@ __global__ void __launch_bounds__(256) clip_avgpool9s8_kernel(const float* x, fl
         int64_t t = i / Q;
         int p = (int)(t % P);
         int64_t f = t / P;
-        y[i * ldy + coff] = avgpool9s8_at(x + clip_image(f, B, T) * H * W, H, W, p, q);
+        y[i * ldy + coff] = avgpool9s8_at<FLIP>(x + clip_image(f, B, T) * H * W, H, W, p, q);
     }
 }
 
@@ -513,10 +523,12 @@ __global__ void __launch_bounds__(256) argmax_kernel(const float* hm, int maps, 
 // P == H and Q == W: no interpolation, the values are read as they are (never staged: each is read once).  A map is addressed
 // by three strides: NHWC as the convolutions leave it (sj = 1, sp = ld, pad channels skipped) or NCHW (sj = H * W, sp = 1).
 constexpr int DECODE_LDS = 12288;   // floats: 48 KB of the 64 KB static LDS limit (46 x 46 = 8.5 KB, 92 x 92 = 34 KB fit)
-template <bool STAGE>
+// CLIP (the video plan): the B * T images are frame-major, image f = t * B + b, and the results of image f go to the batch-major row
+// clip_image(f) = b * T + t of the outputs; everything else is the same code.
+template <bool STAGE, bool CLIP = false>
 __global__ void __launch_bounds__(256) decode_kernel(const float* hm, int64_t sb, int64_t sj, int64_t sp, int J, int H, int W,
                                                      int P, int Q, float sh, float sw, FastDiv fQ, int32_t* idx, float* preds,
-                                                     float* maxvals) {
+                                                     float* maxvals, int cB, int cT) {
     __shared__ float tile[STAGE ? DECODE_LDS : 1];
     __shared__ float red_v[4];
     __shared__ int red_i[4];
@@ -570,11 +582,12 @@ __global__ void __launch_bounds__(256) decode_kernel(const float* hm, int64_t sb
                 bv = red_v[k];
                 bi = red_i[k];
             }
-        if (idx) idx[map] = bi;
+        const int o = CLIP ? (int)clip_image(b, cB, cT) * J + j : map;
+        if (idx) idx[o] = bi;
         float keep = bv > 0.f ? 1.f : 0.f;
-        preds[map * 2] = (float)(bi % Q) * keep;
-        preds[map * 2 + 1] = (float)(bi / Q) * keep;
-        maxvals[map] = bv;
+        preds[o * 2] = (float)(bi % Q) * keep;
+        preds[o * 2 + 1] = (float)(bi / Q) * keep;
+        maxvals[o] = bv;
     }
 }
 
@@ -1061,9 +1074,11 @@ __global__ void __launch_bounds__(256) flip_merge_kernel(const float* a, const f
 // final_preds (utils/extra_utils/evaluation.py:75-97): one wavefront per (b, j) map like argmax_kernel, then lane 0 does the
 // quarter-pixel refinement and the way back through the (2, 3) float64 inverse of the crop transform; every product and sum
 // of that transform is rounded on its own, in numpy's order (no FMA).
+// CLIP: frame-major images, batch-major results and `inv` rows, as in decode_kernel.
+template <bool CLIP>
 __global__ void __launch_bounds__(256) final_preds_kernel(const float* hm, int64_t sb, int64_t sj, int64_t sp, int maps, int J,
                                                           int H, int W, int res0, int res1, const double* inv, float* preds,
-                                                          float* coords, float* maxvals) {
+                                                          float* coords, float* maxvals, int cB, int cT) {
     int map = blockIdx.x * 4 + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     if (map >= maps) return;
@@ -1089,6 +1104,8 @@ __global__ void __launch_bounds__(256) final_preds_kernel(const float* hm, int64
         }
     }
     if (lane != 0) return;
+    const int ob = CLIP ? (int)clip_image(b, cB, cT) : b;     // the row of the results and of `inv`
+    map = ob * J + j;
     maxvals[map] = bv;
     float x = 0.f, y = 0.f;
     if (bv > 0.f) {                 // a NaN maximum masks to 0 as maxval.gt(0) does
@@ -1110,7 +1127,7 @@ __global__ void __launch_bounds__(256) final_preds_kernel(const float* hm, int64
         coords[map * 2 + 1] = y;
     }
     if (inv) {
-        const double* m = inv + (int64_t)b * 6;
+        const double* m = inv + (int64_t)ob * 6;
         const double p0 = (double)x - 1.0, p1 = (double)y - 1.0;
         const double v0 = __dadd_rn(__dadd_rn(__dmul_rn(m[0], p0), __dmul_rn(m[1], p1)), m[2]);
         const double v1 = __dadd_rn(__dadd_rn(__dmul_rn(m[3], p0), __dmul_rn(m[4], p1)), m[5]);
@@ -1166,8 +1183,17 @@ extern "C" int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int 
     UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldy >= C && ldy % 4 == 0 && (uintptr_t)y % 16 == 0,
                UP_ERR_INVALID, "clip_nchw_to_nhwc: bad argument");
     int64_t npix = (int64_t)T * B * H * W;
-    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel, npix, as_stream(stream), x, y, B, T, C, H * W, ldy, npix);
+    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<false>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
     return check_launch("clip_nchw_to_nhwc");
+}
+extern "C" int up_clip_nchw_to_nhwc_flip(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldy >= C && ldy % 4 == 0 && (uintptr_t)y % 16 == 0,
+               UP_ERR_INVALID, "clip_nchw_to_nhwc_flip: bad argument");
+    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "clip_nchw_to_nhwc_flip: %d x %d: a pixel index beyond the int32 range", H,
+               W);
+    int64_t npix = (int64_t)T * B * H * W;
+    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<true>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
+    return check_launch("clip_nchw_to_nhwc_flip");
 }
 extern "C" int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream) {
     UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && (uintptr_t)x % 16 == 0,
@@ -1353,8 +1379,20 @@ extern "C" int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int cof
     UP_REQUIRE(x && y && B > 0 && T > 0 && H > 0 && W > 0 && coff >= 0 && coff < ldy, UP_ERR_INVALID, "clip_avgpool: bad argument");
     UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1, UP_ERR_INVALID, "clip_avgpool: P,Q mismatch");
     int64_t total = (int64_t)T * B * P * Q;
-    UP_LAUNCH_1D(clip_avgpool9s8_kernel, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
+    UP_LAUNCH_1D(clip_avgpool9s8_kernel<false>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
     return check_launch("clip_avgpool9s8");
+}
+
+extern "C" int up_clip_avgpool9s8_flip_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                                           void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && H > 0 && W > 0 && ldy > 0 && coff >= 0 && coff < ldy, UP_ERR_INVALID,
+               "clip_avgpool_flip: bad argument");
+    UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1 && P > 0 && Q > 0, UP_ERR_INVALID,
+               "clip_avgpool_flip: P,Q mismatch");
+    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "clip_avgpool_flip: %d x %d: a pixel index beyond the int32 range", H, W);
+    int64_t total = (int64_t)T * B * P * Q;
+    UP_LAUNCH_1D(clip_avgpool9s8_kernel<true>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
+    return check_launch("clip_avgpool9s8_flip");
 }
 
 extern "C" int up_lstm0_fwd(const float* gates, int ldg, float* cell, float* hide, int ldo, int64_t rows, int Cg,
@@ -1419,11 +1457,35 @@ extern "C" int up_heatmap_decode(const float* hm, int64_t stride_b, int64_t stri
     const float sh = ac_scale(H, P), sw = ac_scale(W, Q);     // as up_bilinear_fwd computes them
     if ((P != H || Q != W) && H * W <= DECODE_LDS)
         hipLaunchKernelGGL(decode_kernel<true>, grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P, Q, sh,
-                           sw, make_fastdiv(Q), idx, preds_xy, maxvals);
+                           sw, make_fastdiv(Q), idx, preds_xy, maxvals, 0, 0);
     else
         hipLaunchKernelGGL(decode_kernel<false>, grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P, Q, sh,
-                           sw, make_fastdiv(Q), idx, preds_xy, maxvals);
+                           sw, make_fastdiv(Q), idx, preds_xy, maxvals, 0, 0);
     return check_launch("heatmap_decode");
+}
+
+extern "C" int up_clip_heatmap_decode(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int T, int J, int H,
+                                      int W, int P, int Q, int32_t* idx, float* preds_xy, float* maxvals, void* stream) {
+    UP_REQUIRE(hm && preds_xy && maxvals, UP_ERR_INVALID, "clip_heatmap_decode: null argument");
+    UP_REQUIRE(B > 0 && T > 0 && J > 0 && H > 0 && W > 0 && stride_b > 0 && stride_j > 0 && stride_p > 0, UP_ERR_INVALID,
+               "clip_heatmap_decode: %d x %d x %d maps of %d x %d, strides %lld / %lld / %lld", B, T, J, H, W, (long long)stride_b,
+               (long long)stride_j, (long long)stride_p);
+    UP_REQUIRE(P >= H && Q >= W, UP_ERR_INVALID, "clip_heatmap_decode: %d x %d -> %d x %d (down-sampling is not decoded)", H, W, P, Q);
+    const int64_t lim = INT32_MAX, N = (int64_t)B * T;
+    UP_REQUIRE((int64_t)P * Q <= lim && N <= lim && N * J * 2 <= lim && (int64_t)H * W <= lim && stride_b <= lim && stride_j <= lim &&
+                   stride_p <= lim && (N - 1) * stride_b <= lim && (J - 1) * stride_j <= lim && ((int64_t)H * W - 1) * stride_p <= lim &&
+                   (N - 1) * stride_b + (J - 1) * stride_j + ((int64_t)H * W - 1) * stride_p <= lim,
+               UP_ERR_INVALID, "clip_heatmap_decode: %d x %d x %d maps of %d x %d -> %d x %d: an index beyond the int32 range", B, T, J,
+               H, W, P, Q);
+    const dim3 grid((int)N * J), block(256);
+    const float sh = ac_scale(H, P), sw = ac_scale(W, Q);
+    if ((P != H || Q != W) && H * W <= DECODE_LDS)
+        hipLaunchKernelGGL((decode_kernel<true, true>), grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P,
+                           Q, sh, sw, make_fastdiv(Q), idx, preds_xy, maxvals, B, T);
+    else
+        hipLaunchKernelGGL((decode_kernel<false, true>), grid, block, 0, as_stream(stream), hm, stride_b, stride_j, stride_p, J, H, W, P,
+                           Q, sh, sw, make_fastdiv(Q), idx, preds_xy, maxvals, B, T);
+    return check_launch("clip_heatmap_decode");
 }
 
 // B x J maps of H x W behind three positive element strides: every count and the offset of the last element within int32
@@ -1476,9 +1538,25 @@ extern "C" int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_
     UP_REQUIRE(maps_in_int32(stride_b, stride_j, stride_p, B, J, H, W) && (int64_t)B * J * 2 <= INT32_MAX, UP_ERR_INVALID,
                "final_preds: %d x %d maps of %d x %d: an index beyond the int32 range", B, J, H, W);
     const int maps = B * J;
-    hipLaunchKernelGGL(final_preds_kernel, dim3(cdiv(maps, 4)), dim3(256), 0, as_stream(stream), hm, stride_b, stride_j, stride_p,
-                       maps, J, H, W, res0, res1, inv, preds_xy, coords_xy, maxvals);
+    hipLaunchKernelGGL(final_preds_kernel<false>, dim3(cdiv(maps, 4)), dim3(256), 0, as_stream(stream), hm, stride_b, stride_j,
+                       stride_p, maps, J, H, W, res0, res1, inv, preds_xy, coords_xy, maxvals, 0, 0);
     return check_launch("final_preds");
+}
+
+extern "C" int up_clip_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int T, int J, int H,
+                                   int W, int res0, int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals,
+                                   void* stream) {
+    UP_REQUIRE(hm && preds_xy && maxvals, UP_ERR_INVALID, "clip_final_preds: null argument");
+    UP_REQUIRE(B > 0 && T > 0 && J > 0 && H > 0 && W > 0 && stride_b > 0 && stride_j > 0 && stride_p > 0 && res0 > 0 && res1 > 0,
+               UP_ERR_INVALID, "clip_final_preds: %d x %d x %d maps of %d x %d, strides %lld / %lld / %lld, res %d, %d", B, T, J, H, W,
+               (long long)stride_b, (long long)stride_j, (long long)stride_p, res0, res1);
+    const int64_t N = (int64_t)B * T;
+    UP_REQUIRE(N <= INT32_MAX && maps_in_int32(stride_b, stride_j, stride_p, (int)N, J, H, W) && N * J * 2 <= INT32_MAX, UP_ERR_INVALID,
+               "clip_final_preds: %d x %d x %d maps of %d x %d: an index beyond the int32 range", B, T, J, H, W);
+    const int maps = (int)N * J;
+    hipLaunchKernelGGL(final_preds_kernel<true>, dim3(cdiv(maps, 4)), dim3(256), 0, as_stream(stream), hm, stride_b, stride_j,
+                       stride_p, maps, J, H, W, res0, res1, inv, preds_xy, coords_xy, maxvals, B, T);
+    return check_launch("clip_final_preds");
 }
 
 extern "C" int up_make_heatmaps(const double* kpt_xy, int B, int K, int H, int W, double stride, double sigma,

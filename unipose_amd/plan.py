@@ -276,6 +276,10 @@ class UniPoseLSTMPlan:
         heat, cell, hide = plan.step(x[:, 0], cm[:, 0])                    # the first frame (LSTM_0) ...
         heat, cell, hide = plan.step(x[:, 1], cm[:, 1], (hide, cell))      # ... a later one: the module's per-frame path
         heats, cell, hide = plan.clip(x, cm)     # (B, T, K+1, h, w) + the last frame's state: the module's whole-clip unroll
+        preds, maxvals, idx, cell, hide = plan.clip_keypoints(x, cm)       # the joints, no NCHW heat-maps in between
+        preds, coords, maxvals = plan.clip_final_preds(x, cm, center, scale, flip=True, pairs=[[1, 2], [3, 4]])
+        state = plan.stream_state()                                        # a camera: one frame in, joints out
+        preds, maxvals, idx = plan.stream(frame, centermap, state, first=True)
 
     The state is the caller's, NCHW (B, K+2, h, w) as the reference's signature has it; the (K+2, h, w) zeros of the reference's
     first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
@@ -286,7 +290,7 @@ class UniPoseLSTMPlan:
         if model.training:
             raise ValueError("UniPoseLSTMPlan captures the inference forward: call model.eval() first")
         # model.stride is not looked at: the reference's video model stores it (model/uniposeLSTM.py:71) and never up-samples, and
-        # neither does the drop-in module (unipose_amd/uniposeLSTM.py).  Decode the heat-maps with ops.heatmap_decode(hm, size).
+        # neither does the drop-in module (unipose_amd/uniposeLSTM.py).  clip_keypoints / stream decode on either grid.
         if batch < 1 or frames < 1 or height < 8 or width < 8:
             raise ValueError(f"UniPoseLSTMPlan: batch {batch}, {frames} frames, {height} x {width} input")
         w0 = model.backbone.conv1.weight
@@ -368,6 +372,134 @@ class UniPoseLSTMPlan:
         _C.check(_C.lib().up_unipose_lstm_clip(self._plan, x.data_ptr(), cm.data_ptr(), heat.data_ptr(), cell.data_ptr(),
                                                hide.data_ptr(), ws, nbytes, self._stream()), "unipose_lstm_clip")
         return heat, cell, hide
+
+    # ---- the evaluation entries: joints, flip test, final_preds, stream ---------------------------------------------------------
+    def _clip_inputs(self, frames, centermaps):
+        B, T, H, W = self.batch, self.frames, self.height, self.width
+        return self._input(frames, (B, T, 3, H, W), "clip"), self._input(centermaps, (B, T, 1, H, W), "centre maps")
+
+    def _tuple_out(self, who, out, names, shapes, dtypes):
+        if out is None:
+            return tuple(torch.empty(s, dtype=d, device=self.device) for s, d in zip(shapes, dtypes))
+        if len(out) != len(names):
+            raise ValueError(f"UniPoseLSTMPlan.{who}: `out` is a ({', '.join(names)}) tuple")
+        return tuple(_check_out("UniPoseLSTMPlan." + who, n, t, s, self.device, d) for n, t, s, d in zip(names, out, shapes, dtypes))
+
+    def _perm(self, dataset, pairs):
+        from . import ops, protocol
+        return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, False, pairs), self.num_classes + 1)
+
+    def _flip_ws(self):
+        """the flip test keeps the first pass's heat-maps while the clip runs again: a larger workspace, made at the first call"""
+        need = max(_C.lib().up_unipose_lstm_plan_flip_workspace(self._plan), 256) + 256
+        if self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws()
+
+    def clip_keypoints(self, frames: torch.Tensor, centermaps: torch.Tensor, full_resolution: bool = False, out=None):
+        """The joints of the whole clip without its NCHW heat-maps (``up_unipose_lstm_clip_keypoints``): (preds (B, T, K+1, 2),
+        maxvals (B, T, K+1, 1), idx (B, T, K+1) int32, cell, hide (B, K+2, h, w) of the last frame) — equal bits to
+        ``ops.heatmap_decode`` of ``clip(...)``'s heat-maps.  full_resolution: on the grid of the maps up-sampled to the input size,
+        else on the maps' own.  `out`: such a 5-tuple to write into."""
+        B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
+        x, cm = self._clip_inputs(frames, centermaps)
+        f32 = torch.float32
+        preds, maxvals, idx, cell, hide = self._tuple_out(
+            "clip_keypoints", out, ("preds", "maxvals", "idx", "cell", "hide"),
+            ((B, T, K + 1, 2), (B, T, K + 1, 1), (B, T, K + 1), (B, K + 2, h, w), (B, K + 2, h, w)), (f32, f32, torch.int32, f32, f32))
+        oh, ow = (self.height, self.width) if full_resolution else (h, w)
+        ws, nbytes = self._ws()
+        _C.check(_C.lib().up_unipose_lstm_clip_keypoints(self._plan, x.data_ptr(), cm.data_ptr(), oh, ow, idx.data_ptr(),
+                                                         preds.data_ptr(), maxvals.data_ptr(), cell.data_ptr(), hide.data_ptr(), ws,
+                                                         nbytes, self._stream()), "unipose_lstm_clip_keypoints")
+        return preds, maxvals, idx, cell, hide
+
+    def clip_flip_heatmaps(self, frames: torch.Tensor, centermaps: torch.Tensor, pairs=None, dataset: str = None,
+                           out: torch.Tensor = None):
+        """The flip test of a clip in one call (``up_unipose_lstm_clip_flip``; this project's extension, the reference's video
+        drivers run none): the network on the clip and on the mirrored clip (frames and centre maps), each with its own recurrent
+        state, the second maps mirrored back with left / right channels exchanged (``protocol.flip_perm(dataset, K, False,
+        pairs)``; the reference has no list for Penn_Action: pass `pairs`), and the mean of the two — equal bits to
+        ``ops.flip_merge`` of the two ``clip`` results frame by frame.  Returns (B, T, K+1, h, w)."""
+        B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
+        x, cm = self._clip_inputs(frames, centermaps)
+        perm = self._perm(dataset, pairs)
+        shape = (B, T, K + 1, h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            _check_out("UniPoseLSTMPlan.clip_flip_heatmaps", "out", out, shape, self.device)
+        ws, nbytes = self._flip_ws()
+        _C.check(_C.lib().up_unipose_lstm_clip_flip(self._plan, x.data_ptr(), cm.data_ptr(), perm, out.data_ptr(), ws, nbytes,
+                                                    self._stream()), "unipose_lstm_clip_flip")
+        return out
+
+    def clip_final_preds(self, frames: torch.Tensor, centermaps: torch.Tensor, center=None, scale=None, res=None, flip: bool = False,
+                         pairs=None, dataset: str = None, out=None):
+        """``ops.final_preds`` of the clip's maps without writing them (``up_unipose_lstm_clip_final_preds``): (preds (B, T, K+1, 2)
+        in source-image pixels, coords (B, T, K+1, 2) on the heat-map grid, maxvals (B, T, K+1, 1)).  `center` (B, T, 2) / `scale`
+        (B, T): one crop per frame (``protocol.inverse_maps``); ``center=None``: preds = coords.  `res` = [w, h] of the maps by
+        default.  flip: the flip test first (``clip_flip_heatmaps``).  `out`: a (preds, coords, maxvals) triple to write into."""
+        from . import protocol
+        B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
+        x, cm = self._clip_inputs(frames, centermaps)
+        perm = self._perm(dataset, pairs) if flip else None
+        res = [w, h] if res is None else protocol._res(res)
+        if int(res[0]) <= 0 or int(res[1]) <= 0:
+            raise ValueError(f"UniPoseLSTMPlan.clip_final_preds: res {list(res)}")
+        inv = None
+        if center is not None:
+            import numpy as np
+            # a tensor stays one (protocol.get_transform keeps the reference's arithmetic in a tensor scale's dtype)
+            c = center if isinstance(center, torch.Tensor) else np.asarray(center)
+            sc = scale if isinstance(scale, torch.Tensor) or scale is None else np.asarray(scale)
+            if sc is None or tuple(c.shape) != (B, T, 2) or tuple(sc.shape) != (B, T):
+                raise ValueError(f"UniPoseLSTMPlan.clip_final_preds: center {tuple(c.shape)} / scale "
+                                 f"{None if sc is None else tuple(sc.shape)}, one crop per frame is {(B, T, 2)} / {(B, T)}")
+            inv = torch.from_numpy(protocol.inverse_maps(c.reshape(B * T, 2), sc.reshape(B * T), res)).to(self.device)
+        shapes = ((B, T, K + 1, 2), (B, T, K + 1, 2), (B, T, K + 1, 1))
+        preds, coords, maxvals = self._tuple_out("clip_final_preds", out, ("preds", "coords", "maxvals"), shapes,
+                                                 (torch.float32,) * 3)
+        ws, nbytes = self._flip_ws() if flip else self._ws()
+        _C.check(_C.lib().up_unipose_lstm_clip_final_preds(self._plan, x.data_ptr(), cm.data_ptr(), perm,
+                                                           None if inv is None else inv.data_ptr(), int(res[0]), int(res[1]),
+                                                           preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
+                                                           self._stream()), "unipose_lstm_clip_final_preds")
+        return preds, coords, maxvals
+
+    def stream_state(self):
+        """A zeroed recurrent-state buffer for ``stream``: opaque bytes (the plan's own NHWC hide and cell), one per camera."""
+        n = _C.lib().up_unipose_lstm_plan_state_bytes(self._plan)
+        buf = torch.zeros(n + 256, dtype=torch.uint8, device=self.device)
+        off = (-buf.data_ptr()) % 256
+        return buf[off:off + n]
+
+    def stream(self, frame: torch.Tensor, centermap: torch.Tensor, state: torch.Tensor, first: bool = False,
+               full_resolution: bool = False, heat: torch.Tensor = None):
+        """One frame in, joints out (``up_unipose_lstm_stream_keypoints``): (preds (B, K+1, 2), maxvals (B, K+1, 1), idx (B, K+1)
+        int32) — equal bits to ``ops.heatmap_decode`` of ``step``'s heat-maps — with hide and cell kept in `state`
+        (``stream_state()``), updated in place.  first: the first frame of a stream (LSTM_0; `state` is not read).  `heat`: an
+        optional (B, K+1, h, w) tensor that receives the NCHW heat-maps."""
+        B, H, W, h, w, K = self.batch, self.height, self.width, self.out_height, self.out_width, self.num_classes
+        x = self._input(frame, (B, 3, H, W), "frame")
+        cm = self._input(centermap, (B, 1, H, W), "centre map")
+        n = _C.lib().up_unipose_lstm_plan_state_bytes(self._plan)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or state.numel() != n
+                or state.device != self.device or not state.is_contiguous() or state.data_ptr() % 256):
+            raise ValueError(f"UniPoseLSTMPlan.stream: `state` is not a buffer of stream_state() ({n} bytes, uint8, 256-byte aligned, "
+                             f"on {self.device})")
+        if heat is not None:
+            _check_out("UniPoseLSTMPlan.stream", "heat", heat, (B, K + 1, h, w), self.device)
+        idx = torch.empty((B, K + 1), dtype=torch.int32, device=self.device)
+        preds = torch.empty((B, K + 1, 2), dtype=torch.float32, device=self.device)
+        maxvals = torch.empty((B, K + 1, 1), dtype=torch.float32, device=self.device)
+        oh, ow = (H, W) if full_resolution else (h, w)
+        ws, nbytes = self._ws()
+        _C.check(_C.lib().up_unipose_lstm_stream_keypoints(self._plan, x.data_ptr(), cm.data_ptr(), state.data_ptr(), int(bool(first)),
+                                                           oh, ow, idx.data_ptr(), preds.data_ptr(), maxvals.data_ptr(),
+                                                           None if heat is None else heat.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_lstm_stream_keypoints")
+        return preds, maxvals, idx
 
     def close(self):
         if self._plan:

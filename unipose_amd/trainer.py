@@ -398,7 +398,12 @@ class Trainer(_TrainerBase):
 
 
 class VideoTrainer(_TrainerBase):
-    """UniPose-LSTM (reference ``uniposeLSTM.py:36-260``).  ``args.augment`` as for ``Trainer``, one draw per clip."""
+    """UniPose-LSTM (reference ``uniposeLSTM.py:36-260``).  ``args.augment`` as for ``Trainer``, one draw per clip.
+
+    ``args.flip_test`` (default off; this project's extension, the reference's video drivers run no flip test): validation unrolls
+    the clip and the mirrored clip (frames and centre maps), merges each frame with ``ops.flip_merge`` and hands the merged maps to
+    ``ops.accuracy``.  The left / right joints come from ``protocol.flip_perm(dataset, K, False, args.flip_pairs)``; the reference
+    has no list for Penn_Action, so ``args.flip_pairs`` ([[a, b], ...], 0-based joints) is needed there (ValueError)."""
     batch_size = 1
     sigma = 1                      # uniposeLSTM.py:53
     frame_memory = 5               # uniposeLSTM.py:43
@@ -421,6 +426,10 @@ class VideoTrainer(_TrainerBase):
         model = unipose_lstm(num_classes=self.numClasses, backbone="resnet", output_stride=16, sync_bn=True,
                              freeze_bn=False, stride=self.stride)
         model.batch_frames = True      # this loop always walks all frames of a clip: trunk once per clip batch, not per frame
+        self.flip_test = bool(getattr(args, "flip_test", False))
+        if self.flip_test:
+            from . import protocol
+            self.flip_perm = protocol.flip_perm(args.dataset, self.numClasses, False, getattr(args, "flip_pairs", None))
         self._setup(model, args, dev)
 
     def _load_pretrained(self, path):
@@ -474,7 +483,16 @@ class VideoTrainer(_TrainerBase):
                 acc, acc_PCK, acc_PCKh, _, _, visible = ops.accuracy(heat, heatmap_var[:, j], 0.2, 0.5, self.dataset)
                 metrics.update(acc, acc_PCK, acc_PCKh, visible, video=True)
 
-            self._unroll(input_var, heatmap_var, centermap_var, on_frame)
+            if not self.flip_test:
+                self._unroll(input_var, heatmap_var, centermap_var, on_frame)
+                continue
+            # the flip test: one unroll after the other (each with its own recurrent state), then frame by frame the merge
+            plain, mirrored = [], []
+            self._unroll(input_var, heatmap_var, centermap_var, lambda j, heat: plain.append(heat))
+            self._unroll(torch.flip(input_var, [-1]), heatmap_var, torch.flip(centermap_var, [-1]),
+                         lambda j, heat: mirrored.append(heat))
+            for j, (a, f) in enumerate(zip(plain, mirrored)):
+                on_frame(j, ops.flip_merge(a, f, self.flip_perm))
         self._after_validation(metrics)
         return metrics
 
