@@ -614,6 +614,35 @@ enum { UP_PIX_U8 = 0, UP_PIX_F32 = 1 };
 int up_augment_image(const void* src_hwc, int src_type, int B, int Hs, int Ws, int C, const int32_t* valid_hw, const double* inv,
                      int frames_per_map, float border, float mean, float stdv, float* out_chw, int Ho, int Wo, void* stream);
 
+/* ---- the crop in front of the network: source frames to the trunk's NHWC input (ABI 10 addition) ----
+ * How a camera frame and a person's centre / scale become the input of the network (the geometry of transforms.py:79-116
+ * get_transform, made by unipose_amd/protocol.py crop_maps; the reference's own crop, transforms.py:128-179, copies an integer window
+ * and resizes it with scipy.misc.imresize, which SciPy has removed: its pixels cannot be reproduced, the pixel contract is this
+ * project's).  up_augment_image's resample, written once as the trunk's NHWC input and, from the same thread, as the mirrored input
+ * of the flip test; nothing is staged in NCHW.
+ * src_hwc (F,Hs,Ws,C) dense, src_type UP_PIX_U8 or UP_PIX_F32, C = 1 .. 4.
+ * frame_of (B) int32 on the device or NULL: sample b reads frame frame_of[b], so several persons share one frame; NULL: sample b
+ *   reads frame b, and F must equal B.  Device data, never trusted: an index outside 0 .. F-1 makes every tap of that sample
+ *   `border` and nothing is loaded for it.
+ * valid_hw (F,2) int32 on the device or NULL: PER SOURCE FRAME, the (height, width) of frame f that holds pixels, cut to 0 .. Hs /
+ *   0 .. Ws as in up_augment_image; what lies beyond it is never read.
+ * inv (B,6) float64 on the device: one map per sample, with the meaning of up_augment_image's inv.
+ * Per output pixel (u, v) and channel c < C: exactly the arithmetic stated for up_augment_image above (float64 coordinates with fma,
+ * the float64 decision whether any tap can be valid, the three fmaf blends, the float32 division (val - mean) / stdv) — one device
+ * function serves both kernels.  y_nhwc[b,v,u,c] and y_flip_nhwc[b,v,Wo-1-u,c] receive the same value, computed once; the pad
+ * channels C <= c < ldy are written as zeros, as up_nchw_to_nhwc writes them.  Either output may be NULL, not both.
+ * Contract: y_nhwc has equal bits to up_nchw_to_nhwc(up_augment_image(src[frame_of], valid_hw[frame_of], ...)), y_flip_nhwc to
+ * up_nchw_to_nhwc_flip of the same.
+ * One thread per output pixel, consecutive threads consecutive u; a pixel's ldy channels leave as 16-byte stores (with ldy = 4 a
+ * wavefront writes 1 KiB of consecutive pixels per instruction, in either direction); 64-bit indexing; no LDS; a grid of at most
+ * 2^21 threads walks larger outputs in further trips.
+ * UP_ERR_INVALID (nothing launched): null src_hwc / inv, both outputs NULL, y_nhwc == y_flip_nhwc, an unknown src_type, F, B, Hs,
+ * Ws, Ho or Wo <= 0, C outside 1 .. 4, ldy < C or ldy % 4 != 0, an output that is not 16-byte aligned, frame_of == NULL with
+ * F != B, stdv <= 0 (or NaN). */
+int up_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of, const int32_t* valid_hw,
+                    const double* inv, int B, float border, float mean, float stdv, float* y_nhwc, float* y_flip_nhwc, int Ho, int Wo,
+                    int ldy, void* stream);
+
 /* ---- PCK / PCKh evaluation (utils/evaluate.py:5-29 calc_dists / dist_acc, :58-172 accuracy) ----
  * From the joint coordinates of the predicted and the target heat-maps (two up_heatmap_argmax calls), entirely on
  * the device: per joint the fraction of counted samples (both target coordinates > 1) whose normalised distance is
@@ -709,7 +738,20 @@ int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int
  * A perm entry outside 0 .. out_channels-1, res <= 0, a null pointer, unset weights or a too-small workspace are refused before
  * anything is launched.  up_unipose_plan_program_workspace(plan, k): the need of program k alone, in the order of this comment
  * (0 forward, 1 upsampled, 2 keypoints, 3 persons, 4 flip_forward, 5 final_preds with and 6 without the flip test), 0 for any
- * other k: up_unipose_plan_workspace() is the largest of 0..3, up_unipose_plan_flip_workspace() of 4..6. */
+ * other k: up_unipose_plan_workspace() is the largest of 0..3, up_unipose_plan_flip_workspace() of 4..6.
+ * From source frames: two entries put up_crop_to_nhwc (C = 3, B = batch, Ho x Wo = H x W, ldy = 4) in front of these programs, in
+ * place of their layout pass — in the flip test ONE launch fills the input and the mirrored input, and the source is read once per
+ * person.  src_hwc .. stdv are up_crop_to_nhwc's arguments (crop_inv its inv); every convolution launch is the one the
+ * corresponding program above makes, so with equal crop bits the results are equal bit for bit.
+ *   up_unipose_frame_heatmaps     heat_nchw (batch, out_channels, ceil(H/8), ceil(W/8)): up_unipose_forward's result, or with
+ *                                 perm_host != NULL up_unipose_flip_forward's, of the cropped input.
+ *   up_unipose_frame_final_preds  up_unipose_final_preds of the cropped input; perm_host == NULL: no flip test.  inv, res0, res1:
+ *                                 the way back as there (protocol.inverse_maps on the heat-map grid), independent of crop_inv.
+ * Refused before anything is launched: what up_crop_to_nhwc refuses, and what the entries above refuse.  The mirrored input stays
+ * alive through the first trunk, so the flip forms need more than up_unipose_plan_flip_workspace(): the need of each is
+ * up_unipose_plan_program_workspace(plan, UP_PROGRAM_FROM_FRAMES + k), k = 0, 4, 5, 6 naming the program it otherwise equals (0 for
+ * any other k); neither up_unipose_plan_workspace() nor up_unipose_plan_flip_workspace() changes. */
+enum { UP_PROGRAM_FROM_FRAMES = 256 };
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
     int32_t batch, height, width;   /* input (batch, 3, height, width) */
@@ -738,6 +780,13 @@ int up_unipose_flip_forward(up_unipose_plan* plan, const float* x_nchw, const in
 int up_unipose_final_preds(up_unipose_plan* plan, const float* x_nchw, const int32_t* perm_host, const double* inv, int res0,
                            int res1, float* preds_xy, float* coords_xy, float* maxvals, void* workspace, size_t workspace_bytes,
                            void* stream);
+int up_unipose_frame_heatmaps(up_unipose_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws, const int32_t* frame_of,
+                              const int32_t* valid_hw, const double* crop_inv, float border, float mean, float stdv,
+                              const int32_t* perm_host, float* heat_nchw, void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_frame_final_preds(up_unipose_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                 const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border, float mean,
+                                 float stdv, const int32_t* perm_host, const double* inv, int res0, int res1, float* preds_xy,
+                                 float* coords_xy, float* maxvals, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- whole-clip and per-frame inference entry of UniPose-LSTM (ABI 10 additions) ----------------------------------------
  * The video network (model/uniposeLSTM.py:67-138: the image trunk with the video WASP, ConvLSTM, five-convolution head) with

@@ -919,6 +919,14 @@ def g21_final_preds():
                raises IndexError; those are listed in index_error (H, W, res0, res1);
       x_*      the exact-integer case: res 16, scale 16 * 4 / 200, integer centres: every transformed value an exact integer;
       fb<k>_*  flip_back (MPII, 16 channels): in, out."""
+    mods = _ref_extra_utils()
+    E, T = mods["evaluation"], mods["transforms"]
+    _g21_record(E, T)
+
+
+def _ref_extra_utils():
+    """the genuine utils/extra_utils modules, loaded by file path under a private package name with this project's stand-ins (see
+    g21_final_preds)"""
     import types
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import cv2_standin
@@ -946,7 +954,10 @@ def g21_final_preds():
         sys.modules[spec.name] = m
         spec.loader.exec_module(m)
         mods[name] = m
-    E, T = mods["evaluation"], mods["transforms"]
+    return mods
+
+
+def _g21_record(E, T):
     rng = np.random.default_rng(21)
     out, raised = {}, []
 
@@ -1024,6 +1035,37 @@ def g21_final_preds():
     save("g21_final_preds.npz", shapes=np.array(shapes, dtype=np.int64), **out)
 
 
+def g22_crop_geometry():
+    """G22: the geometry of the crop in front of the network (utils/extra_utils/transforms.py).  The genuine get_transform and
+    transform, loaded as for G21.  For res in [368, 368], [52, 68], [64, 64] (get_transform's order [H, W]), rot in 0, 30, -45 and B
+    centres / scales as float32 tensors (c32, s32) and as float64 arrays (c64, s64), stacked as (R, ROT, B, ...): T<kind> =
+    get_transform, Ti<kind> = its inverse, ul<kind> = transform([0, 0], ..., invert=1, rot) and br<kind> = transform(res, ...,
+    invert=1, rot): the window's corners, lines 150-152 of crop.  The pixels of crop cannot be recorded: scipy.misc.imresize is gone."""
+    T = _ref_extra_utils()["transforms"]
+    rng = np.random.default_rng(22)
+    B = 4
+    res_list, rots = [[368, 368], [52, 68], [64, 64]], [0, 30, -45]
+    c64 = rng.uniform(60.0, 900.0, (B, 2))
+    s64 = rng.uniform(0.3, 3.0, B)
+    c32, s32 = torch.tensor(c64, dtype=torch.float32), torch.tensor(s64, dtype=torch.float32)
+    out = {"res": np.array(res_list, dtype=np.int64), "rot": np.array(rots, dtype=np.int64), "c32": c32.numpy(), "s32": s32.numpy(),
+           "c64": c64, "s64": s64}
+    for kind, c, s in (("32", c32, s32), ("64", c64, s64)):
+        acc = {k: [] for k in ("T", "Ti", "ul", "br")}
+        for res in res_list:
+            for rot in rots:
+                mats = [T.get_transform(c[i], s[i], res, rot=rot) for i in range(B)]
+                acc["T"].append(np.stack(mats))
+                acc["Ti"].append(np.stack([np.linalg.inv(m) for m in mats]))
+                acc["ul"].append(np.stack([T.transform([0, 0], c[i], s[i], res, invert=1, rot=rot) for i in range(B)]))
+                acc["br"].append(np.stack([T.transform(res, c[i], s[i], res, invert=1, rot=rot) for i in range(B)]))
+        for k, v in acc.items():
+            v = np.stack(v)
+            out[k + kind] = v.reshape((len(res_list), len(rots)) + v.shape[1:])
+    assert out["ul64"].dtype.kind == "i" and out["T32"].dtype == np.float64
+    save("g22_crop_geometry.npz", **out)
+
+
 def g0_keys():
     """G0: the reference's state_dict contract (names, shapes, dtypes, order) for both models."""
     import json
@@ -1037,10 +1079,10 @@ def g0_keys():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22"]
     fns = dict(g0=g0_keys, g1=g1_eval_full, g2=g2_taps, g4=g4_train, g5=g5_lstm, g6=g6_argmax, g7=g7_accuracy,
                g8=g8_targets, g9=g9_multi_person, g10=g10_eval_736, g11=g11_train_b8, g12=g12_eval_os8, g13=g13_bf16_yardstick,
                g14=g14_train_368, g15=g15_lstm_train, g16=g16_trajectory, g17=g17_decode_full_res, g18=g18_accuracy_rect,
-               g19=g19_box_targets, g20=g20_augment, g21=g21_final_preds)
+               g19=g19_box_targets, g20=g20_augment, g21=g21_final_preds, g22=g22_crop_geometry)
     for w in which:
         fns[w]()

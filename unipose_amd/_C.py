@@ -151,7 +151,8 @@ SIGNATURES = {
     "up_make_gaussian_maps": (_i, [_p, _i, _i, _i, C.c_double, _p, _p]),
     "up_normalize_image": (_i, [_p, _i, _i, _i, _i, _f, _f, _p, _p]),
     "up_augment_image": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _f, _f, _f, _p, _i, _i, _p]),
-    "up_pck_accuracy": (_i, [_p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
+    "up_crop_to_nhwc": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _p, _p, _i, _i, _i, _p]),
+    "up_pck_accuracy":(_i, [_p, _p, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     "up_peak_mask": (_i, [_p, _i, _i, _i, _p, _p]),
     "up_box_argmax": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "up_persons_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
@@ -170,7 +171,10 @@ SIGNATURES = {
     "up_unipose_plan_program_workspace": (_sz, [_p, _i]),
     "up_unipose_flip_forward": (_i, [_p, _p, C.POINTER(C.c_int32), _p, _p, _sz, _p]),
     "up_unipose_final_preds": (_i, [_p, _p, C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
-    "up_clip_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "up_unipose_frame_heatmaps": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, C.POINTER(C.c_int32), _p, _p, _sz, _p]),
+    "up_unipose_frame_final_preds": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p,
+                                          _p, _sz, _p]),
+    "up_clip_nchw_to_nhwc":(_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "up_unipose_lstm_plan_create": (_i, [_p, C.POINTER(_p)]),
@@ -200,6 +204,8 @@ SIGNATURES = {
     "up_profile_live_flops": (_i, [C.POINTER(C.c_double), _i]),
     "up_profile_end": (_i, [C.POINTER(C.c_double), _i]),
 }
+
+PROGRAM_FROM_FRAMES = 256          # UP_PROGRAM_FROM_FRAMES: up_unipose_plan_program_workspace(plan, 256 + k), k = 0, 4, 5, 6
 
 _lib = None
 # Set ONLY by tests/conftest.py when it points the binding at the CPU emulation build of the same

@@ -76,6 +76,8 @@ enum Kind {
     PERSONS,               // the multi-person decode straight from the NHWC heat-maps (up_persons_decode), on their own grid
     // the evaluation protocol (ABI 10 additions): the mirrored layout pass, the flip test's combine step, final_preds from NHWC
     TO_NHWC_FLIP, MERGE, FINAL,
+    // the crop in front of the network (ABI 10 addition): source frames to the trunk's input and, in `aux`, its mirror (up_crop_to_nhwc)
+    CROP,
     // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL,
     // its evaluation entries (ABI 10 additions): the mirrored clip layout and pooling, decode / final_preds of frame-major maps
@@ -352,33 +354,45 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
 // activations — every convolution launch is the one HEAT_MAPS makes — the first pass's heat-maps staying alive through the second,
 // then up_flip_merge into the caller's NCHW tensor; FLIP_PREDS: the same, merged in place (NHWC), then up_final_preds; PREDS: one
 // pass, then up_final_preds.  All three work on the heat-maps' own grid.
-enum ImageForm { HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM, FLIP_HEAT, FLIP_PREDS, PREDS, IMAGE_FORMS };
+// From source frames (up_unipose_frame_heatmaps / up_unipose_frame_final_preds): FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS and
+// FRAME_PREDS are HEAT_MAPS, FLIP_HEAT, FLIP_PREDS and PREDS with ONE up_crop_to_nhwc launch in place of the layout pass(es): it
+// fills the trunk's input and, in the flip forms, the mirrored input too, which then stays alive through the first trunk.
+enum ImageForm {
+    HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM, FLIP_HEAT, FLIP_PREDS, PREDS,
+    FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS, FRAME_PREDS, IMAGE_FORMS
+};
 
 static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
     const int n = c.batch;
     int h = c.height, w = c.width;
-    // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC)
-    Ref x;
+    const bool frame = form >= FRAME_HEAT;
+    if (frame) form = form == FRAME_HEAT ? HEAT_MAPS : form == FRAME_FLIP_HEAT ? FLIP_HEAT : form == FRAME_FLIP_PREDS ? FLIP_PREDS : PREDS;
+    const bool flip = form == FLIP_HEAT || form == FLIP_PREDS;
+    // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC); from frames: the crop writes NHWC itself, and the mirror beside it
+    Ref x, m;
     x.id = p.tensor(n, h, w, 4);
+    if (frame && flip) m.id = p.tensor(n, h, w, 4);
     {
         Op op;
-        op.kind = TO_NHWC;
+        op.kind = frame ? CROP : TO_NHWC;
         op.out = x;
+        op.aux = m;
         op.ext = X;
         op.n = n; op.c = 3;
         p.push(op);
     }
     x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
-    if (form == FLIP_HEAT || form == FLIP_PREDS) {
+    if (flip) {
         int h2 = c.height, w2 = c.width;
-        Ref m;
-        m.id = p.tensor(n, h2, w2, 4);
         Op op;
-        op.kind = TO_NHWC_FLIP;
-        op.out = m;
-        op.ext = X;
-        op.n = n; op.c = 3;
-        p.push(op);
+        if (!frame) {
+            m.id = p.tensor(n, h2, w2, 4);
+            op.kind = TO_NHWC_FLIP;
+            op.out = m;
+            op.ext = X;
+            op.n = n; op.c = 3;
+            p.push(op);
+        }
         m = trunk(p, m, n, h2, w2, c.output_stride, c.out_channels, false);
         op = Op();
         op.kind = MERGE;
@@ -639,6 +653,12 @@ struct Io {
     float* coords = nullptr;
     float* state = nullptr;          // STATE_IN / STATE_OUT: the caller's buffer, hide then cell, state_half elements each
     size_t state_half = 0;
+    const void* src = nullptr;       // CROP: the arguments of up_crop_to_nhwc
+    int src_type = 0, frames = 0, src_h = 0, src_w = 0;
+    const int32_t* frame_of = nullptr;
+    const int32_t* valid_hw = nullptr;
+    const double* crop_inv = nullptr;
+    float border = 0.f, mean = 0.f, stdv = 0.f;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -695,6 +715,10 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             break;
         case TO_NHWC_FLIP:
             e = up_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            break;
+        case CROP:
+            e = up_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.c, io.frame_of, io.valid_hw, io.crop_inv, op.n,
+                                io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
             break;
         case MERGE: {
             const Tensor& t = T_(op.in);
@@ -773,9 +797,13 @@ struct up_unipose_plan {
     Plan p;                    // HEAT_MAPS; its convolutions are the listed ones and own the weight store
     Plan up, kp, ps;           // UPSAMPLED, KEYPOINTS, PERSONS_FORM: the same trunk, so the same convolutions in the same order
     Plan fh, fp, pr;           // FLIP_HEAT, FLIP_PREDS (the trunk twice: every convolution name twice), PREDS
+    Plan rh, rfh, rfp, rpr;    // FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS, FRAME_PREDS: their needs are reported per program only
     size_t ws_bytes = 0;       // the largest of the first four
-    size_t flip_ws_bytes = 0;  // the largest of the last three
-    Plan* prog(int form) { Plan* const all[up::plan::IMAGE_FORMS] = {&p, &up, &kp, &ps, &fh, &fp, &pr}; return all[form]; }
+    size_t flip_ws_bytes = 0;  // the largest of the next three
+    Plan* prog(int form) {
+        Plan* const all[up::plan::IMAGE_FORMS] = {&p, &up, &kp, &ps, &fh, &fp, &pr, &rh, &rfh, &rfp, &rpr};
+        return all[form];
+    }
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
@@ -792,6 +820,7 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
             delete pl;
             return e;
         }
+        if (f >= plan::FRAME_HEAT) continue;
         size_t& need = f < plan::FLIP_HEAT ? pl->ws_bytes : pl->flip_ws_bytes;
         need = std::max(need, pl->prog(f)->ws_bytes);
     }
@@ -870,7 +899,16 @@ extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return 
 extern "C" size_t up_unipose_plan_flip_workspace(const up_unipose_plan* pl) { return pl ? pl->flip_ws_bytes : 0; }
 
 extern "C" size_t up_unipose_plan_program_workspace(const up_unipose_plan* pl, int program) {
-    return pl && program >= 0 && program < plan::IMAGE_FORMS ? const_cast<up_unipose_plan*>(pl)->prog(program)->ws_bytes : 0;
+    if (!pl) return 0;
+    int form = program;
+    if (program >= UP_PROGRAM_FROM_FRAMES) {     // the program that starts from source frames, named by the one it otherwise equals
+        const int k = program - UP_PROGRAM_FROM_FRAMES;
+        form = k == plan::HEAT_MAPS ? plan::FRAME_HEAT : k == plan::FLIP_HEAT ? plan::FRAME_FLIP_HEAT
+               : k == plan::FLIP_PREDS ? plan::FRAME_FLIP_PREDS : k == plan::PREDS ? plan::FRAME_PREDS : -1;
+    } else if (program >= plan::FRAME_HEAT) {
+        form = -1;
+    }
+    return form >= 0 ? const_cast<up_unipose_plan*>(pl)->prog(form)->ws_bytes : 0;
 }
 
 static int image_ready(const up_unipose_plan* pl, const Plan& prog, const void* workspace, size_t ws_bytes, const char* what) {
@@ -985,6 +1023,73 @@ extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, 
     io.coords = coords_xy;
     io.maxvals = maxvals;
     return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_final_preds");
+}
+
+// From source frames (ABI 10 additions): the crop of up_crop_to_nhwc in front of the same programs.  Its own refusals (source type,
+// sizes, frame_of == NULL with F != batch, std) come from its wrapper, which is the program's first launch: nothing runs before it.
+static int frame_io(const up_unipose_plan* pl, plan::Io& io, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                    const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border, float mean, float stdv,
+                    const char* what) {
+    UP_REQUIRE(src_hwc && crop_inv, UP_ERR_INVALID, "%s: null source frames or crop maps", what);
+    UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "%s: source type %d", what, src_type);
+    UP_REQUIRE(F > 0 && Hs > 0 && Ws > 0, UP_ERR_INVALID, "%s: %d frames of %d x %d", what, F, Hs, Ws);
+    UP_REQUIRE(frame_of || F == pl->cfg.batch, UP_ERR_INVALID, "%s: no frame_of with %d frames for a batch of %d", what, F,
+               pl->cfg.batch);
+    UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "%s: std %g", what, (double)stdv);
+    io.src = src_hwc;
+    io.src_type = src_type;
+    io.frames = F;
+    io.src_h = Hs;
+    io.src_w = Ws;
+    io.frame_of = frame_of;
+    io.valid_hw = valid_hw;
+    io.crop_inv = crop_inv;
+    io.border = border;
+    io.mean = mean;
+    io.stdv = stdv;
+    return UP_OK;
+}
+
+extern "C" int up_unipose_frame_heatmaps(up_unipose_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                         const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                         float mean, float stdv, const int32_t* perm_host, float* heat_nchw, void* workspace,
+                                         size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && heat_nchw && workspace, UP_ERR_INVALID, "unipose_frame_heatmaps: null argument");
+    plan::Io io;
+    if (int e = frame_io(pl, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, "unipose_frame_heatmaps"))
+        return e;
+    if (perm_host)
+        if (int e = perm_ok(pl, perm_host, "unipose_frame_heatmaps")) return e;
+    const Plan& prog = perm_host ? pl->rfh : pl->rh;
+    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_frame_heatmaps")) return e;
+    io.perm = perm_host;
+    io.heat = heat_nchw;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_frame_heatmaps");
+}
+
+extern "C" int up_unipose_frame_final_preds(up_unipose_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                            const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                            float mean, float stdv, const int32_t* perm_host, const double* inv, int res0, int res1,
+                                            float* preds_xy, float* coords_xy, float* maxvals, void* workspace, size_t ws_bytes,
+                                            void* stream) {
+    UP_REQUIRE(pl && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_frame_final_preds: null argument");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_frame_final_preds: res %d, %d", res0, res1);
+    plan::Io io;
+    if (int e = frame_io(pl, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv,
+                         "unipose_frame_final_preds"))
+        return e;
+    if (perm_host)
+        if (int e = perm_ok(pl, perm_host, "unipose_frame_final_preds")) return e;
+    const Plan& prog = perm_host ? pl->rfp : pl->rpr;
+    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_frame_final_preds")) return e;
+    io.perm = perm_host;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_frame_final_preds");
 }
 
 // ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------

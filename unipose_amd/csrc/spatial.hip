@@ -882,6 +882,40 @@ __global__ void __launch_bounds__(256) normalize_image_kernel(const float* img, 
 // valid extent is the border constant and is not loaded.  Store-bound: the four taps of neighbouring threads share cache lines.
 __device__ __forceinline__ float aug_px(const float* p) { return *p; }
 __device__ __forceinline__ float aug_px(const uint8_t* p) { return (float)*p; }
+// One output pixel (column u, row v) of a sample under the map m, read from source image `img` of valid extent Hv x Wv (Hv = Wv = 0:
+// no image, every tap is border): val[c] = the normalised value of channel c < C, 0 for C <= c < 4.  The ONE statement of the
+// resample's arithmetic: up_augment_image and up_crop_to_nhwc both store what this returns.
+template <typename T>
+__device__ __forceinline__ void aug_sample(const T* src, int64_t img, int Hs, int Ws, int C, int Hv, int Wv, const double* m, int u,
+                                           int v, float border, float mean, float stdv, float out[4]) {
+    const double sx = fma(m[0], (double)u, fma(m[1], (double)v, m[2]));
+    const double sy = fma(m[3], (double)u, fma(m[4], (double)v, m[5]));
+    const double x0d = floor(sx), y0d = floor(sy);
+    // decided in float64 (false for NaN and for anything too large to index): otherwise all four taps are border
+    const bool near = x0d >= -1.0 && x0d <= (double)(Wv - 1) && y0d >= -1.0 && y0d <= (double)(Hv - 1);
+    float val[4] = {border, border, border, border};
+    if (near) {
+        const int x0 = (int)x0d, y0 = (int)y0d;      // -1 .. Wv-1, -1 .. Hv-1
+        const float fx = (float)(sx - x0d), fy = (float)(sy - y0d);
+        const bool xa = x0 >= 0, xb = x0 + 1 < Wv, ya = y0 >= 0, yb = y0 + 1 < Hv;
+        const int64_t p = ((img * Hs + y0) * Ws + x0) * C;        // may lie before the image: read at valid taps only
+        const int64_t row = (int64_t)Ws * C;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c < C) {
+                const float v00 = ya && xa ? aug_px(src + p + c) : border;
+                const float v01 = ya && xb ? aug_px(src + p + C + c) : border;
+                const float v10 = yb && xa ? aug_px(src + p + row + c) : border;
+                const float v11 = yb && xb ? aug_px(src + p + row + C + c) : border;
+                const float top = fmaf(fx, v01 - v00, v00);
+                const float bot = fmaf(fx, v11 - v10, v10);
+                val[c] = fmaf(fy, bot - top, top);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[c] = c < C ? (val[c] - mean) / stdv : 0.f;
+}
 template <typename T>
 __global__ void __launch_bounds__(256) augment_image_kernel(const T* src, int Hs, int Ws, int C, const int32_t* valid_hw,
                                                             const double* inv, int frames_per_map, float border, float mean,
@@ -892,42 +926,60 @@ __global__ void __launch_bounds__(256) augment_image_kernel(const T* src, int Hs
         const int64_t t = e / Wo;
         const int v = (int)(t % Ho);
         const int64_t b = t / Ho;
-        const double* m = inv + (b / frames_per_map) * 6;
         int Hv = Hs, Wv = Ws;
         if (valid_hw) {                                  // device data: cut to the buffer, never trusted beyond it
             Hv = min(max(valid_hw[2 * b], 0), Hs);
             Wv = min(max(valid_hw[2 * b + 1], 0), Ws);
         }
-        const double sx = fma(m[0], (double)u, fma(m[1], (double)v, m[2]));
-        const double sy = fma(m[3], (double)u, fma(m[4], (double)v, m[5]));
-        const double x0d = floor(sx), y0d = floor(sy);
-        // decided in float64 (false for NaN and for anything too large to index): otherwise all four taps are border
-        const bool near = x0d >= -1.0 && x0d <= (double)(Wv - 1) && y0d >= -1.0 && y0d <= (double)(Hv - 1);
-        float val[4] = {border, border, border, border};
-        if (near) {
-            const int x0 = (int)x0d, y0 = (int)y0d;      // -1 .. Wv-1, -1 .. Hv-1
-            const float fx = (float)(sx - x0d), fy = (float)(sy - y0d);
-            const bool xa = x0 >= 0, xb = x0 + 1 < Wv, ya = y0 >= 0, yb = y0 + 1 < Hv;
-            const int64_t p = ((b * Hs + y0) * Ws + x0) * C;          // may lie before the sample: read at valid taps only
-            const int64_t row = (int64_t)Ws * C;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (c < C) {
-                    const float v00 = ya && xa ? aug_px(src + p + c) : border;
-                    const float v01 = ya && xb ? aug_px(src + p + C + c) : border;
-                    const float v10 = yb && xa ? aug_px(src + p + row + c) : border;
-                    const float v11 = yb && xb ? aug_px(src + p + row + C + c) : border;
-                    const float top = fmaf(fx, v01 - v00, v00);
-                    const float bot = fmaf(fx, v11 - v10, v10);
-                    val[c] = fmaf(fy, bot - top, top);
-                }
-            }
-        }
+        float val[4];
+        aug_sample(src, b, Hs, Ws, C, Hv, Wv, inv + (b / frames_per_map) * 6, u, v, border, mean, stdv, val);
         const int64_t hw = (int64_t)Ho * Wo;
         float* o = out + b * C * hw + (int64_t)v * Wo + u;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            if (c < C) o[c * hw] = (val[c] - mean) / stdv;
+            if (c < C) o[c * hw] = val[c];
+    }
+}
+// The crop in front of the network (up_crop_to_nhwc, include/unipose_hip.h): up_augment_image's resample written straight into the
+// trunk's NHWC input and, from the same thread, into the mirrored input of the flip test.  Sample b reads source frame frame_of[b]
+// (several persons of one frame share it); an index outside 0 .. F-1 is device data and makes the sample all border, nothing loaded.
+// One thread per output pixel, consecutive threads consecutive u: with ld = 4 a wave stores 1 KiB of consecutive pixels per
+// instruction, forwards into y and backwards into y_flip; the quads beyond the first are the zero pad channels.
+template <typename T>
+__global__ void __launch_bounds__(256) crop_to_nhwc_kernel(const T* src, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                                           const int32_t* valid_hw, const double* inv, float border, float mean,
+                                                           float stdv, float* y, float* yf, int Ho, int Wo, int ld,
+                                                           long long total /* B*Ho*Wo */) {
+    UP_GRID_STRIDE(e, total) {
+        const int u = (int)(e % Wo);
+        const int64_t t = e / Wo;
+        const int v = (int)(t % Ho);
+        const int64_t b = t / Ho;
+        int64_t f = frame_of ? (int64_t)frame_of[b] : b;
+        int Hv = 0, Wv = 0;
+        if (f >= 0 && f < F) {
+            Hv = Hs;
+            Wv = Ws;
+            if (valid_hw) {                              // per source frame; device data: cut to the buffer
+                Hv = min(max(valid_hw[2 * f], 0), Hs);
+                Wv = min(max(valid_hw[2 * f + 1], 0), Ws);
+            }
+        } else {
+            f = 0;                                       // no such frame: no tap is valid, no address is used
+        }
+        float val[4];
+        aug_sample(src, f, Hs, Ws, C, Hv, Wv, inv + b * 6, u, v, border, mean, stdv, val);
+        const float4 q = make_float4(val[0], val[1], val[2], val[3]), z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (y) {
+            float* d = y + e * ld;
+            *reinterpret_cast<float4*>(d) = q;
+            for (int c = 4; c < ld; c += 4) *reinterpret_cast<float4*>(d + c) = z;
+        }
+        if (yf) {
+            float* d = yf + (e - u + (Wo - 1 - u)) * ld;
+            *reinterpret_cast<float4*>(d) = q;
+            for (int c = 4; c < ld; c += 4) *reinterpret_cast<float4*>(d + c) = z;
+        }
     }
 }
 
@@ -1622,6 +1674,32 @@ extern "C" int up_augment_image(const void* src_hwc, int src_type, int B, int Hs
                            (const float*)src_hwc, Hs, Ws, C, valid_hw, inv, frames_per_map, border, mean, stdv, out_chw, Ho, Wo,
                            total);
     return check_launch("augment_image");
+}
+extern "C" int up_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                               const int32_t* valid_hw, const double* inv, int B, float border, float mean, float stdv, float* y_nhwc,
+                               float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream) {
+    UP_REQUIRE(src_hwc && inv, UP_ERR_INVALID, "crop_to_nhwc: null argument");
+    UP_REQUIRE(y_nhwc || y_flip_nhwc, UP_ERR_INVALID, "crop_to_nhwc: both outputs are null");
+    UP_REQUIRE(y_nhwc != y_flip_nhwc, UP_ERR_INVALID, "crop_to_nhwc: y_nhwc == y_flip_nhwc");
+    UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "crop_to_nhwc: source type %d", src_type);
+    UP_REQUIRE(F > 0 && B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, UP_ERR_INVALID,
+               "crop_to_nhwc: %d samples from %d frames of %d x %d to %d x %d", B, F, Hs, Ws, Ho, Wo);
+    UP_REQUIRE(C >= 1 && C <= 4, UP_ERR_INVALID, "crop_to_nhwc: %d channels (1 .. 4)", C);
+    UP_REQUIRE(ldy >= C && ldy % 4 == 0, UP_ERR_INVALID, "crop_to_nhwc: ldy %d for %d channels (a multiple of 4)", ldy, C);
+    UP_REQUIRE((uintptr_t)y_nhwc % 16 == 0 && (uintptr_t)y_flip_nhwc % 16 == 0, UP_ERR_INVALID,
+               "crop_to_nhwc: an output that is not 16-byte aligned");
+    UP_REQUIRE(frame_of || F == B, UP_ERR_INVALID, "crop_to_nhwc: no frame_of with %d frames for %d samples", F, B);
+    UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "crop_to_nhwc: std %g", (double)stdv);
+    const long long total = (long long)B * Ho * Wo;
+    if (src_type == UP_PIX_U8)
+        hipLaunchKernelGGL(crop_to_nhwc_kernel<uint8_t>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
+                           (const uint8_t*)src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho,
+                           Wo, ldy, total);
+    else
+        hipLaunchKernelGGL(crop_to_nhwc_kernel<float>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
+                           (const float*)src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho,
+                           Wo, ldy, total);
+    return check_launch("crop_to_nhwc");
 }
 
 extern "C" int up_peak_mask(const float* maps, int nmaps, int H, int W, uint8_t* mask, void* stream) {

@@ -2017,6 +2017,59 @@ def augment_image(pixels: torch.Tensor, inv, out_hw, border: float = 128.0, mean
     return out
 
 
+def crop_to_nhwc(frames: torch.Tensor, inv, out_hw, frame_of=None, valid_hw=None, flip: bool = False, ld: int = 4,
+                 border: float = 128.0, mean: float = 128.0, std: float = 256.0):
+    """The crop in front of the network in one launch (``up_crop_to_nhwc``, include/unipose_hip.h): frames (F,Hs,Ws,C) uint8 or
+    float32 on the device, C = 1 .. 4; inv (B, 6) or (B, 2, 3), any array-like, kept in float64: per sample the affine map from an
+    output pixel (u, v, 1) to its position in the source frame (``protocol.crop_maps`` makes it); out_hw = (Ho, Wo).  frame_of (B,)
+    names the frame each sample reads (several persons of one frame share it; None: sample b reads frame b); valid_hw (F, 2) =
+    (height, width) per FRAME for frames padded into one buffer.  Returns y (B,Ho,Wo,ld) float32 NHWC, ``(value - mean) / std``
+    with zero pad channels — equal bits to the layout pass of ``augment_image(frames[frame_of], ...)`` — or with `flip` the pair
+    (y, y_flip), y_flip the horizontally mirrored y, written by the same launch.  Maps and frame indices are handled as in
+    ``augment_image``: given on the host they are checked here (non-finite entries and indices outside 0 .. F-1 are refused);
+    device tensors pass unchecked, and the kernel makes such a sample all border and reads nothing for it."""
+    _dev_ok(frames)
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"crop_to_nhwc: uint8 or float32 frames, got {frames.dtype}")
+    if frames.dim() != 4:
+        raise ValueError(f"crop_to_nhwc: frames (F,H,W,C), got {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    nf, h, w, c = x.shape
+    m = torch.as_tensor(inv, dtype=torch.float64) if not (isinstance(inv, torch.Tensor) and inv.is_cuda) else None
+    if m is not None and not bool(torch.isfinite(m).all()):
+        raise ValueError("crop_to_nhwc: a map with a non-finite entry")
+    m = _as_f64(inv if m is None else m, x.device)
+    if m.dim() == 3 and tuple(m.shape[1:]) == (2, 3):
+        m = m.reshape(-1, 6)
+    if m.dim() != 2 or m.shape[1] != 6 or m.shape[0] < 1:
+        raise ValueError(f"crop_to_nhwc: maps {tuple(m.shape)} ((B, 6) or (B, 2, 3) expected)")
+    b = m.shape[0]
+    fo = None
+    if frame_of is not None:
+        on_device = isinstance(frame_of, torch.Tensor) and frame_of.is_cuda
+        fo = torch.as_tensor(frame_of)
+        if tuple(fo.shape) != (b,):
+            raise ValueError(f"crop_to_nhwc: frame_of {tuple(fo.shape)} for {b} maps")
+        if not on_device and not bool(((fo >= 0) & (fo < nf)).all()):
+            raise ValueError(f"crop_to_nhwc: a frame index outside 0 .. {nf - 1}")
+        fo = fo.to(device=x.device, dtype=torch.int32).contiguous()
+    elif nf != b:
+        raise ValueError(f"crop_to_nhwc: {b} maps for {nf} frames and no frame_of")
+    valid = None
+    if valid_hw is not None:
+        valid = torch.as_tensor(valid_hw).to(device=x.device, dtype=torch.int32).contiguous()
+        if tuple(valid.shape) != (nf, 2):
+            raise ValueError(f"crop_to_nhwc: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    shape = (b, max(ho, 0), max(wo, 0), max(int(ld), 0))
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    yf = torch.empty(shape, dtype=torch.float32, device=x.device) if flip else None
+    _C.check(_C.lib().up_crop_to_nhwc(x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, h, w, c, _ptr(fo), _ptr(valid), m.data_ptr(),
+                                      b, float(border), float(mean), float(std), y.data_ptr(), _ptr(yf), ho, wo, int(ld), _stream(x)),
+             "crop_to_nhwc")
+    return (y, yf) if flip else y
+
+
 DATASET_IDS = {"LSP": 0, "COCO": 1, "Penn_Action": 2, "NTID": 3, "PoseTrack": 4, "BBC": 5, "MPII": 6}
 
 

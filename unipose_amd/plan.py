@@ -14,6 +14,7 @@ and returns the heat-maps (the two slices of ``unipose(bbox=True)`` when the mod
     preds, maxvals, idx = plan.keypoints(images)     # equal bits to ops.heatmap_argmax(heat), without the NCHW heat-maps
     kpts, count, status = plan.persons(images, "MPII")        # bbox=True models: ops.persons_decode of the maps, without them
     preds, coords, maxvals = plan.final_preds(images, center, scale, flip=True, dataset="MPII")   # flip test + pytorch-pose's final_preds
+    preds, coords, maxvals = plan.frame_final_preds(frames_u8_hwc, center, scale, frame_of=[0] * 8, flip=True, dataset="MPII")   # the crop too
 
 A model built with ``stride != 8`` (the reference's full-resolution mode, model/unipose.py:31-32) gives the heat-maps up-sampled
 to the input size, as the module does; ``keypoints`` then decodes on that grid without ever writing the up-sampled maps
@@ -247,6 +248,93 @@ class UniPosePlan:
         _C.check(_C.lib().up_unipose_final_preds(self._plan, x.data_ptr(), perm, None if inv is None else inv.data_ptr(), int(res[0]),
                                                  int(res[1]), preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
                                                  self._stream()), "unipose_final_preds")
+        return preds, coords, maxvals
+
+    # ---- from source frames: the crop (up_crop_to_nhwc) in front of the same programs ----------------------------------------------
+    def _frame_ws(self, program):
+        """a program from frames keeps the mirrored input through the first trunk: its own need, made at the first call (`_flip_ws`)"""
+        need = max(_C.lib().up_unipose_plan_program_workspace(self._plan, _C.PROGRAM_FROM_FRAMES + program), 256) + 256
+        if self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def _frame_args(self, who, frames, center, scale, frame_of, rot, valid_hw):
+        """the arguments of up_crop_to_nhwc as the two entries take them, and the tensors that must outlive the call"""
+        from . import protocol
+        if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.device != self.device
+                or frames.dtype not in (torch.uint8, torch.float32)):
+            raise ValueError(f"UniPosePlan.{who}: frames (F, Hs, Ws, 3) uint8 or float32 on {self.device}, got "
+                             f"{tuple(frames.shape)} {frames.dtype} on {frames.device}")
+        x = frames.contiguous()
+        nf, hs, ws = x.shape[:3]
+        if center is None or scale is None or len(center) != self.batch or len(scale) != self.batch:
+            raise ValueError(f"UniPosePlan.{who}: one centre and one scale per sample of the batch of {self.batch}")
+        m = torch.from_numpy(protocol.crop_maps(center, scale, [self.height, self.width], rot)).to(self.device)
+        fo = None
+        if frame_of is not None:
+            fo = torch.as_tensor(frame_of)
+            if tuple(fo.shape) != (self.batch,):
+                raise ValueError(f"UniPosePlan.{who}: frame_of {tuple(fo.shape)} for a batch of {self.batch}")
+            fo = fo.to(device=self.device, dtype=torch.int32).contiguous()
+        elif nf != self.batch:
+            raise ValueError(f"UniPosePlan.{who}: {nf} frames for a batch of {self.batch} and no frame_of")
+        valid = None
+        if valid_hw is not None:
+            valid = torch.as_tensor(valid_hw).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(valid.shape) != (nf, 2):
+                raise ValueError(f"UniPosePlan.{who}: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
+        args = (x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, hs, ws, None if fo is None else fo.data_ptr(),
+                None if valid is None else valid.data_ptr(), m.data_ptr(), 128.0, 128.0, 256.0)
+        return args, (x, m, fo, valid)
+
+    def frame_heatmaps(self, frames: torch.Tensor, center, scale, frame_of=None, rot=0, flip: bool = False, dataset: str = None,
+                       pairs=None, valid_hw=None, out: torch.Tensor = None):
+        """The heat-maps of persons in source frames in one call (``up_unipose_frame_heatmaps``): frames (F, Hs, Ws, 3) uint8 or
+        float32 on the device as the camera gives them, `center` (B, 2) / `scale` (B,) one person per sample, frame_of (B,) the
+        frame each person is in (None: sample b is in frame b).  The crop is ``protocol.crop_maps(center, scale, [H, W], rot)``
+        sampled as ``ops.crop_to_nhwc`` does (border = mean = 128, std = 256): no NCHW input is staged and each person reads the
+        frame once.  Returns ONE (B, out_channels, h, w) tensor on the maps' own grid: equal bits to the plan's maps of the
+        cropped input, with `flip` to ``flip_heatmaps`` of it (`dataset` / `pairs` as there)."""
+        args, keep = self._frame_args("frame_heatmaps", frames, center, scale, frame_of, rot, valid_hw)
+        perm = self._perm(dataset, pairs) if flip else None
+        shape = (self.batch, self.out_channels, self.map_height, self.map_width)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            _check_out("UniPosePlan.frame_heatmaps", "out", out, shape, self.device)
+        ws, nbytes = self._frame_ws(4 if flip else 0)
+        _C.check(_C.lib().up_unipose_frame_heatmaps(self._plan, *args, perm, out.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_frame_heatmaps")
+        del keep
+        return out
+
+    def frame_final_preds(self, frames: torch.Tensor, center, scale, frame_of=None, rot=0, flip: bool = False, dataset: str = None,
+                          pairs=None, valid_hw=None, out=None, res=None):
+        """Frames, centres and scales in, joints in frame coordinates out (``up_unipose_frame_final_preds``): the crop of
+        ``frame_heatmaps``, the network (with `flip` the flip test), then ``final_preds`` — (preds (B, C, 2) in source-frame
+        pixels, coords (B, C, 2) on the heat-map grid, maxvals (B, C, 1)), equal bits to ``final_preds`` of the cropped input.
+        The way back is ``protocol.inverse_maps(center, scale, res)`` with `res` = [W, H] of the maps by default, as in
+        ``final_preds``; a rotation is not undone on the way back, as in pytorch-pose (``transform_preds`` passes rot = 0)."""
+        from . import protocol
+        args, keep = self._frame_args("frame_final_preds", frames, center, scale, frame_of, rot, valid_hw)
+        perm = self._perm(dataset, pairs) if flip else None
+        res = [self.map_width, self.map_height] if res is None else protocol._res(res)
+        inv = torch.from_numpy(protocol.inverse_maps(center, scale, res)).to(self.device)
+        B, C_ = self.batch, self.out_channels
+        shapes = ((B, C_, 2), (B, C_, 2), (B, C_, 1))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        elif len(out) != 3:
+            raise ValueError("UniPosePlan.frame_final_preds: `out` is a (preds, coords, maxvals) triple")
+        preds, coords, maxvals = (_check_out("UniPosePlan.frame_final_preds", n, t, s, self.device)
+                                  for n, t, s in zip(("preds", "coords", "maxvals"), out, shapes))
+        ws, nbytes = self._frame_ws(5 if flip else 6)
+        _C.check(_C.lib().up_unipose_frame_final_preds(self._plan, *args, perm, inv.data_ptr(), int(res[0]), int(res[1]),
+                                                       preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
+                                                       self._stream()), "unipose_frame_final_preds")
+        del keep
         return preds, coords, maxvals
 
     def close(self):

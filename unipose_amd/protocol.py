@@ -94,3 +94,19 @@ def inverse_maps(center, scale, res):
     for i in range(n):
         out[i] = np.linalg.inv(get_transform(center[i], scale[i], res))[:2]
     return out
+
+
+def crop_maps(center, scale, res, rot=0):
+    """The crop in front of the network, for a batch: (B, 6) float64, the first two rows of
+    ``np.linalg.inv(get_transform(center[i], scale[i], res, rot))`` flattened — the `inv` argument of ``up_crop_to_nhwc``: it takes
+    an output pixel (u, v) of the network input to its position in the source frame.  `res` = [H, W] of the network input:
+    get_transform's own order, where res[1] scales x — NOT the [W, H] that ``final_preds`` (and so ``inverse_maps`` on the way
+    back) wants on non-square maps; ``up_final_preds``'s header records that quirk of the reference.  No +-1 shift: the
+    reference's ``transform`` maps ``pt - 1`` and adds 1, so in 0-based pixels the matrix itself is the map.  `rot` in degrees, one
+    value or one per sample."""
+    n = len(center)
+    rots = np.broadcast_to(np.asarray(rot, dtype=np.float64), (n,))
+    out = np.empty((n, 6), dtype=np.float64)
+    for i in range(n):
+        out[i] = np.linalg.inv(get_transform(center[i], scale[i], res, float(rots[i])))[:2].reshape(6)
+    return out
