@@ -1,24 +1,26 @@
-// Whole-graph inference entry of the UniPose image network ("whole-graph up_unipose_forward fast path"; ABI 9).
+// Whole-graph inference entries of the two networks ("whole-graph up_unipose_forward fast path"; ABI 10).
 //
-// The reference runs its validation / test loops as `heat = model(input)` (unipose.py:150-160); through this entry the same
+// The reference runs its validation / test loops as `heat = model(input)` (unipose.py:150-160); through these entries the same
 // forward — ResNet-101 (resnet.py:44-124) + WASP (wasp.py:66-90) + decoder (decoder.py:38-56) with every BatchNorm folded
 // into its convolution (checkpoint.fold_batchnorm) — is ONE C call on one stream: no Python, no autograd, no allocation.
 // Everything below goes through the PUBLIC C ABI of this library (up_conv2d_fwd, up_maxpool3s2_fwd, up_bilinear_fwd, ...): it is at
-// the same time the example of how a C / C++ application drives the kernels.  The plan owns the packed
-// weight images and biases (device memory, freed by up_unipose_plan_destroy); activations live in a caller-provided workspace
-// whose size up_unipose_plan_workspace() reports (tensor lifetimes are planned, buffers are reused).
+// the same time the example of how a C / C++ application drives the kernels.  A plan owns the packed
+// weight images and biases (device memory, freed by its destroy); activations live in a caller-provided workspace whose size
+// the plan reports (tensor lifetimes are planned, buffers are reused).
 //
-// The launches, their order, their descriptors and their epilogues are exactly those of the drop-in module's folded inference
-// forward (unipose_amd/unipose.py + modules.py after checkpoint.load_folded), so the two produce equal bits
-// (tests/test_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
-// The image plan keeps four programs (and the three of the evaluation protocol, see ImageForm) over one weight store: the heat-maps (up_unipose_forward), the heat-maps up-sampled to the
-// input size as the module does at stride != 8 (up_unipose_forward_upsampled), the joints decoded straight from the NHWC
-// output of the last convolution (up_unipose_keypoints -> up_heatmap_decode; tests/test_heat_decode_*.py), and the persons of
-// the box head decoded from the same NHWC output (up_unipose_persons -> up_persons_decode; tests/test_persons_*.py).
+// The launches, their order, their descriptors and their epilogues are exactly those of the drop-in modules' folded inference
+// forwards (unipose_amd/unipose.py, uniposeLSTM.py + modules.py after checkpoint.load_folded), so the two produce equal bits
+// (tests/test_plan_*.py, tests/test_lstm_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
 //
-// The video network UniPose-LSTM (model/uniposeLSTM.py) has its entry here too (up_unipose_lstm_*, ABI 10 additions): the same
-// trunk builder with the video WASP, then the centre-map hand-over, the ConvLSTM cell and the head — per frame with the caller's
-// state (the module's per-frame path) or for a whole clip (its batch_frames unroll), equal bits again (tests/test_lstm_plan_*.py).
+// What the file holds, top to bottom:
+//   Plan        one program: tensors, convolutions, ops, and the first-fit workspace layout over the tensors' live ranges
+//   trunk       the builder both networks share
+//   Program     what a program is made of (input, passes, ending, recurrent state), its public number and the workspace figure it
+//               counts toward; IMAGE_PROGRAMS and LSTM_PROGRAMS are the two tables, build() and build_lstm() read one row each
+//   run         the launches of one program, with the caller's tensors of the call in an Io
+//   Weights     one store per distinct parameter and the list of convolutions the caller sets, for both plans
+//   launch      "weights set, workspace large enough, then run", and the argument checks both plans make
+//   up_unipose_*, up_unipose_lstm_*    the C entries: each checks its own required pointers, fills its Io and launches one program
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -66,32 +68,30 @@ struct Conv {
     up_conv_desc d;
     int relu;
     bool has_bias;         // the folded network has a bias on every convolution but wasp.conv2
-    float* w_fwd = nullptr;
+    float* w_fwd = nullptr;   // the plan's store of that name (Weights::bind)
     float* bias = nullptr;
-    bool set = false;
 };
+// one Kind per C function called (STATE_IN / STATE_OUT: up_copy2d from / to the caller's state buffer)
 enum Kind {
-    TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW,
-    DECODE,                // key points straight from the NHWC heat-maps (up_heatmap_decode), on the grid the call names
-    PERSONS,               // the multi-person decode straight from the NHWC heat-maps (up_persons_decode), on their own grid
-    // the evaluation protocol (ABI 10 additions): the mirrored layout pass, the flip test's combine step, final_preds from NHWC
-    TO_NHWC_FLIP, MERGE, FINAL,
-    // the crop in front of the network (ABI 10 addition): source frames to the trunk's input and, in `aux`, its mirror (up_crop_to_nhwc)
-    CROP,
-    // the video plan (ABI 10 additions): centre-map pooling, the ConvLSTM gates, and the clip layout (frame-major inside)
-    POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL,
-    // its evaluation entries (ABI 10 additions): the mirrored clip layout and pooling, decode / final_preds of frame-major maps
-    // into batch-major results, the recurrent state of a stream from and to the caller's buffer
-    CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL, STATE_IN, STATE_OUT
+    TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW, DECODE, PERSONS, TO_NHWC_FLIP, MERGE, FINAL, CROP,
+    POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL, CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL,
+    STATE_IN, STATE_OUT
 };
 enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
+// Sizes, strides and physical channel counts come from the tensors an op names; the fields below are what they do not hold.
 struct Op {
     Kind kind;
     Ref in, out, res, aux;
-    int conv = -1;
-    int n = 0;                        // images the op runs on (batch, or T * batch in the clip's trunk and head)
-    Ext ext = X;                      // TO_NHWC / TO_NCHW / POOL and their clip forms: the caller's tensor
-    int a = 0, b = 0, c = 0, e = 0;   // kind-specific integers (see run)
+    int conv = -1;             // CONV: index into the program's convolutions
+    Ext ext = X;               // the layout passes and MERGE: the caller's tensor
+    int n = 0;                 // images the launch works on: the batch B, or T * B in the clip's trunk and head
+    int frames = 1;            // the clip kinds: T
+    int ch = 0;                // logical channels the launch reads or writes (<= the tensors' physical ones)
+    int coff = 0;              // the pooling kinds: the channel of `out` the pooled centre map goes to
+    int src_h = 0, src_w = 0;  // the pooling kinds: size of the caller's centre maps
+    int lds = 0, ldd = 0;      // COPY: row strides of source and destination, in elements
+    int64_t rows = 0;          // COPY: rows of `ch` elements
+    int half = 0;              // STATE_IN / STATE_OUT: 0 the hidden state, 1 the cell state of the caller's buffer
 };
 
 struct Plan {
@@ -145,18 +145,33 @@ struct Plan {
         push(op);
         return out;
     }
+    // an op from a tensor into a new one of out_h x out_w and as many channels: the two poolings and the bilinear resize
+    Ref resample(Kind kind, Ref in, int out_h, int out_w, size_t res_elem = 0) {
+        const Tensor t = tensors[in.id];
+        Op op;
+        op.kind = kind;
+        op.in = in;
+        op.out.id = tensor(t.n, out_h, out_w, t.c);
+        if (res_elem) op.res.id = tensor(t.n, out_h, out_w, t.c, res_elem);
+        op.n = t.n;
+        push(op);
+        return op.out;
+    }
+    Ref maxpool(Ref in) {      // 3x3 stride 2 with its uint8 index tensor
+        return resample(MAXPOOL, in, (tensors[in.id].h - 1) / 2 + 1, (tensors[in.id].w - 1) / 2 + 1, 1);
+    }
     void zero(Ref t) {
         Op op;
         op.kind = ZERO;
         op.out = t;
         push(op);
     }
-    void copy(Ref src, int lds, Ref dst, int ldd, size_t dst_ch, long long rows, int ch) {
+    void copy(Ref src, int lds, Ref dst, int ldd, size_t dst_ch, int64_t rows, int ch) {
         Op op;
         op.kind = COPY;
         op.in = src; op.out = dst;
         op.out.elems += dst_ch;
-        op.a = lds; op.b = ldd; op.c = ch; op.e = (int)rows;
+        op.lds = lds; op.ldd = ldd; op.rows = rows; op.ch = ch;
         push(op);
     }
     // workspace layout: first fit over the live ranges, buffers of dead tensors are reused
@@ -236,22 +251,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     }
     // stem: 7x7 s2 + folded bn1 + ReLU, 3x3 s2 max-pool (resnet.py:113-117)
     x = p.conv("backbone.conv1", x, n, h, w, 4, 3, 64, 7, 2, 3, 1, 1, true);
-    h = p.tensors[x.id].h;
-    w = p.tensors[x.id].w;
-    auto maxpool = [&](Ref in, int hh, int ww, int ch) {
-        Ref out, idx;
-        const int ph = (hh - 1) / 2 + 1, pw = (ww - 1) / 2 + 1;
-        out.id = p.tensor(n, ph, pw, ch);
-        idx.id = p.tensor(n, ph, pw, ch, 1);
-        Op op;
-        op.kind = MAXPOOL;
-        op.in = in; op.out = out; op.res = idx;
-        op.n = n;
-        op.a = hh; op.b = ww; op.c = ch;
-        p.push(op);
-        return out;
-    };
-    x = maxpool(x, h, w, 64);
+    x = p.maxpool(x);
     h = p.tensors[x.id].h;
     w = p.tensors[x.id].w;
     // layer1..4 (resnet.py:76-111): (3, 4, 23, 3) blocks, multi-grid (1, 2, 4) in layer4
@@ -292,48 +292,28 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     Ref y = p.conv("wasp.conv2", stack, 4 * n, h, w, 256, 256, 256, 1, 1, 0, 1, 0, false);
     y = p.conv("wasp.conv2", y, 4 * n, h, w, 256, 256, 256, 1, 1, 0, 1, 0, false);   // the SAME weight again (wasp.py:72-80)
     // global-average-pool branch: GAP -> 1x1 (+ folded BatchNorm) + ReLU -> bilinear 1x1 -> h x w (a broadcast)
-    Ref g;
-    g.id = p.tensor(n, 1, 1, 2048);
-    {
-        Op op;
-        op.kind = GAP;
-        op.in = x; op.out = g;
-        op.n = n;
-        op.a = h * w; op.c = 2048;
-        p.push(op);
-    }
+    Ref g = p.resample(GAP, x, 1, 1);
     g = p.conv("wasp.global_avg_pool.1", g, n, 1, 1, 2048, 2048, 256, 1, 1, 0, 1, 1, !video);
-    auto bilinear = [&](Ref in, int hh, int ww, int ch, int ph, int pw) {
-        Ref out;
-        out.id = p.tensor(n, ph, pw, ch);
-        Op op;
-        op.kind = BILINEAR;
-        op.in = in; op.out = out;
-        op.n = n;
-        op.a = hh; op.b = ww; op.c = ch; op.e = ph * 65536 + pw;
-        p.push(op);
-        return out;
-    };
-    g = bilinear(g, 1, 1, 256, h, w);
+    g = p.resample(BILINEAR, g, h, w);
     Ref cat;
     cat.id = p.tensor(n, h, w, 1280);
     for (int i = 0; i < 4; ++i) {
         Ref s = y;
         s.elems = i * branch;
-        p.copy(s, 256, cat, 1280, (size_t)i * 256, (long long)n * h * w, 256);
+        p.copy(s, 256, cat, 1280, (size_t)i * 256, (int64_t)n * h * w, 256);
     }
-    p.copy(g, 256, cat, 1280, 1024, (long long)n * h * w, 256);
+    p.copy(g, 256, cat, 1280, 1024, (int64_t)n * h * w, 256);
     x = p.conv("wasp.conv1", cat, n, h, w, 1280, 1280, 256, 1, 1, 0, 1, 1, true);   // + folded bn1 + ReLU; dropout is the identity in eval
     // decoder (decoder.py:38-56)
     Ref lw = p.conv("decoder.conv1", low, n, low_h, low_w, 256, 256, 48, 1, 1, 0, 1, 1, true);
-    lw = maxpool(lw, low_h, low_w, 48);
+    lw = p.maxpool(lw);
     const int dh = p.tensors[lw.id].h, dw = p.tensors[lw.id].w;
-    x = bilinear(x, h, w, 256, dh, dw);
+    x = p.resample(BILINEAR, x, dh, dw);
     Ref cat2;
     cat2.id = p.tensor(n, dh, dw, 320);      // 256 + 48 = 304 real channels, zero-padded to a multiple of 32
     p.zero(cat2);
-    p.copy(x, 256, cat2, 320, 0, (long long)n * dh * dw, 256);
-    p.copy(lw, 48, cat2, 320, 256, (long long)n * dh * dw, 48);
+    p.copy(x, 256, cat2, 320, 0, (int64_t)n * dh * dw, 256);
+    p.copy(lw, 48, cat2, 320, 256, (int64_t)n * dh * dw, 48);
     x = p.conv("decoder.last_conv.0", cat2, n, dh, dw, 320, 304, 256, 3, 1, 1, 1, 1, true);
     x = p.conv("decoder.last_conv.4", x, n, dh, dw, 256, 256, 256, 3, 1, 1, 1, 1, true);
     Ref heat;
@@ -346,127 +326,131 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     return p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, out_channels, 1, 1, 0, 1, 0, true, Ref(), heat);
 }
 
-// One program of the image plan over one weight store (like the video plan's LstmForm below).  HEAT_MAPS: the module's forward at
-// stride 8; UPSAMPLED: at stride != 8, the heat-maps bilinearly up-sampled to the input size before the layout pass
-// (model/unipose.py:31-32; unipose_amd/unipose.py forward); KEYPOINTS: the trunk, then up_heatmap_decode on its NHWC output;
-// PERSONS_FORM: the trunk, then up_persons_decode on its NHWC output.
-// The evaluation protocol (utils/extra_utils): FLIP_HEAT: the trunk on x and on the mirrored x (up_nchw_to_nhwc_flip) over the same
-// activations — every convolution launch is the one HEAT_MAPS makes — the first pass's heat-maps staying alive through the second,
-// then up_flip_merge into the caller's NCHW tensor; FLIP_PREDS: the same, merged in place (NHWC), then up_final_preds; PREDS: one
-// pass, then up_final_preds.  All three work on the heat-maps' own grid.
-// From source frames (up_unipose_frame_heatmaps / up_unipose_frame_final_preds): FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS and
-// FRAME_PREDS are HEAT_MAPS, FLIP_HEAT, FLIP_PREDS and PREDS with ONE up_crop_to_nhwc launch in place of the layout pass(es): it
-// fills the trunk's input and, in the flip forms, the mirrored input too, which then stays alive through the first trunk.
-enum ImageForm {
-    HEAT_MAPS, UPSAMPLED, KEYPOINTS, PERSONS_FORM, FLIP_HEAT, FLIP_PREDS, PREDS,
-    FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS, FRAME_PREDS, IMAGE_FORMS
+// ---- what a program is made of ---------------------------------------------------------------------------------------------------
+enum Input { IN_NCHW, IN_FRAMES, IN_CLIP };    // the caller's NCHW batch; source frames through up_crop_to_nhwc; a (B, T, ...) clip
+enum Ending {
+    END_HEAT,          // NCHW heat-maps on their own grid
+    END_UPSAMPLED,     // ... bilinearly up-sampled to the input size first, as the module does at stride != 8 (model/unipose.py:31-32)
+    END_DECODE,        // key points straight from the NHWC maps (up_heatmap_decode), on the grid the call names
+    END_PERSONS,       // the multi-person decode straight from the NHWC maps (up_persons_decode), on their own grid
+    END_FINAL          // up_final_preds straight from the NHWC maps
+};
+enum Counts { COUNTS_OWN, COUNTS_PLAIN, COUNTS_FLIP };    // toward neither figure, workspace() or flip_workspace()
+enum State { STATE_NONE, STATE_NCHW, STATE_BUFFER };      // the recurrent state: none, the caller's NCHW tensors, its opaque NHWC buffer
+struct Program {
+    int number;        // as up_*_plan_program_workspace() takes it
+    Input input;
+    bool flip;         // the flip test: the network on the input and on its mirror over the same activations, then up_flip_merge
+    Ending end;
+    Counts counts;
+    State from = STATE_NONE, to = STATE_NONE;     // the video plan: where the state of the frame before comes from (none: LSTM_0)
+                                                  // and where the new one goes
 };
 
-static int build(Plan& p, const up_unipose_config& c, ImageForm form) {
+// The image plan.  Every convolution launch of a flip program is one the plain program makes, the first pass's heat-maps staying alive
+// through the second.  From frames ONE up_crop_to_nhwc launch stands in place of the layout pass(es): it fills the trunk's input
+// and, in the flip programs, the mirrored input too, which then stays alive through the first trunk — so those need more than
+// flip_workspace() and report their need per program only.  All but UPSAMPLED and DECODE work on the heat-maps' own grid.
+static const Program IMAGE_PROGRAMS[] = {
+    {0, IN_NCHW, false, END_HEAT, COUNTS_PLAIN},        // up_unipose_forward; its convolutions are the listed ones
+    {1, IN_NCHW, false, END_UPSAMPLED, COUNTS_PLAIN},   // up_unipose_forward_upsampled
+    {2, IN_NCHW, false, END_DECODE, COUNTS_PLAIN},      // up_unipose_keypoints
+    {3, IN_NCHW, false, END_PERSONS, COUNTS_PLAIN},     // up_unipose_persons
+    {4, IN_NCHW, true, END_HEAT, COUNTS_FLIP},          // up_unipose_flip_forward
+    {5, IN_NCHW, true, END_FINAL, COUNTS_FLIP},         // up_unipose_final_preds with ...
+    {6, IN_NCHW, false, END_FINAL, COUNTS_FLIP},        // ... and without the flip test
+    {UP_PROGRAM_FROM_FRAMES + 0, IN_FRAMES, false, END_HEAT, COUNTS_OWN},     // up_unipose_frame_heatmaps
+    {UP_PROGRAM_FROM_FRAMES + 4, IN_FRAMES, true, END_HEAT, COUNTS_OWN},
+    {UP_PROGRAM_FROM_FRAMES + 5, IN_FRAMES, true, END_FINAL, COUNTS_OWN},     // up_unipose_frame_final_preds
+    {UP_PROGRAM_FROM_FRAMES + 6, IN_FRAMES, false, END_FINAL, COUNTS_OWN},
+};
+// UniPose-LSTM (model/uniposeLSTM.py:67-138; the drop-in module unipose_amd/uniposeLSTM.py after checkpoint.load_folded).  The step
+// programs are the module's per-frame path (batch_frames = False) for iter == 0 (LSTM_0) resp. iter > 0 with the caller's NCHW
+// state; the clip programs its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True), the flip test running the
+// whole clip twice, each pass with its own recurrent state, so a flip program returns none.  The stream programs are the step
+// programs with the state in the caller's buffer and up_heatmap_decode at the end; their NCHW heat-maps are optional.
+static const Program LSTM_PROGRAMS[] = {
+    {0, IN_NCHW, false, END_HEAT, COUNTS_PLAIN, STATE_NONE, STATE_NCHW},        // up_unipose_lstm_step, the first frame ...
+    {1, IN_NCHW, false, END_HEAT, COUNTS_PLAIN, STATE_NCHW, STATE_NCHW},        // ... and a later one
+    {2, IN_CLIP, false, END_HEAT, COUNTS_PLAIN, STATE_NONE, STATE_NCHW},        // up_unipose_lstm_clip
+    {3, IN_CLIP, false, END_DECODE, COUNTS_PLAIN, STATE_NONE, STATE_NCHW},      // up_unipose_lstm_clip_keypoints
+    {4, IN_CLIP, true, END_HEAT, COUNTS_FLIP},          // up_unipose_lstm_clip_flip
+    {5, IN_CLIP, true, END_FINAL, COUNTS_FLIP},         // up_unipose_lstm_clip_final_preds with ...
+    {6, IN_CLIP, false, END_FINAL, COUNTS_PLAIN},       // ... and without the flip test
+    {7, IN_NCHW, false, END_DECODE, COUNTS_PLAIN, STATE_NONE, STATE_BUFFER},    // up_unipose_lstm_stream_keypoints, first ...
+    {8, IN_NCHW, false, END_DECODE, COUNTS_PLAIN, STATE_BUFFER, STATE_BUFFER},  // ... and not
+};
+template <size_t N>
+static int find(const Program (&table)[N], Input input, bool flip, Ending end, State from = STATE_NONE) {
+    for (size_t i = 0; i < N; ++i)
+        if (table[i].input == input && table[i].flip == flip && table[i].end == end && table[i].from == from) return (int)i;
+    return -1;
+}
+template <size_t N>
+static size_t program_workspace(const Program (&table)[N], const Plan* prog, int number) {
+    for (size_t i = 0; i < N; ++i)
+        if (table[i].number == number) return prog[i].ws_bytes;
+    return 0;
+}
+
+static void build(Plan& p, const up_unipose_config& c, const Program& g) {
     const int n = c.batch;
     int h = c.height, w = c.width;
-    const bool frame = form >= FRAME_HEAT;
-    if (frame) form = form == FRAME_HEAT ? HEAT_MAPS : form == FRAME_FLIP_HEAT ? FLIP_HEAT : form == FRAME_FLIP_PREDS ? FLIP_PREDS : PREDS;
-    const bool flip = form == FLIP_HEAT || form == FLIP_PREDS;
+    const bool frames = g.input == IN_FRAMES;
     // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC); from frames: the crop writes NHWC itself, and the mirror beside it
     Ref x, m;
     x.id = p.tensor(n, h, w, 4);
-    if (frame && flip) m.id = p.tensor(n, h, w, 4);
-    {
-        Op op;
-        op.kind = frame ? CROP : TO_NHWC;
-        op.out = x;
-        op.aux = m;
-        op.ext = X;
-        op.n = n; op.c = 3;
-        p.push(op);
-    }
+    if (frames && g.flip) m.id = p.tensor(n, h, w, 4);
+    Op op;
+    op.kind = frames ? CROP : TO_NHWC;
+    op.out = x;
+    op.aux = m;
+    op.ext = X;
+    op.n = n; op.ch = 3;
+    p.push(op);
     x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
-    if (flip) {
+    if (g.flip) {
         int h2 = c.height, w2 = c.width;
-        Op op;
-        if (!frame) {
+        if (!frames) {
             m.id = p.tensor(n, h2, w2, 4);
+            op = Op();
             op.kind = TO_NHWC_FLIP;
             op.out = m;
             op.ext = X;
-            op.n = n; op.c = 3;
+            op.n = n; op.ch = 3;
             p.push(op);
         }
         m = trunk(p, m, n, h2, w2, c.output_stride, c.out_channels, false);
         op = Op();
-        op.kind = MERGE;
+        op.kind = MERGE;                         // straight into the caller's NCHW tensor, or ...
         op.in = x; op.aux = m;
-        if (form == FLIP_PREDS) op.out = x;      // in place: out == a with equal strides
+        if (g.end == END_FINAL) op.out = x;      // ... in place: out == a with equal strides
         op.ext = HEAT;
-        op.n = n; op.c = c.out_channels;
+        op.n = n; op.ch = c.out_channels;
         p.push(op);
     }
-    if (form == FLIP_PREDS || form == PREDS) {
-        Op op;
-        op.kind = FINAL;
-        op.in = x;
-        op.n = n; op.c = c.out_channels;
-        p.push(op);
-    }
-    if (form == FLIP_HEAT || form == FLIP_PREDS || form == PREDS) {
-        p.layout();
-        return UP_OK;
-    }
-    if (form == KEYPOINTS || form == PERSONS_FORM) {
-        Op op;
-        op.kind = form == KEYPOINTS ? DECODE : PERSONS;
-        op.in = x;
-        op.n = n; op.c = c.out_channels;
-        p.push(op);
-        p.layout();
-        return UP_OK;
-    }
-    if (form == UPSAMPLED) {
-        const int ld = p.tensors[x.id].c;
-        Ref up;
-        up.id = p.tensor(n, c.height, c.width, ld);
-        Op op;
-        op.kind = BILINEAR;
-        op.in = x; op.out = up;
-        op.n = n;
-        op.a = h; op.b = w; op.c = ld; op.e = c.height * 65536 + c.width;
-        p.push(op);
-        x = up;
-    }
-    {
-        Op op;
-        op.kind = TO_NCHW;
+    if (g.end == END_UPSAMPLED) x = p.resample(BILINEAR, x, c.height, c.width);
+    if (!(g.flip && g.end == END_HEAT)) {        // (there the merge has written the caller's heat-maps)
+        op = Op();
+        op.kind = g.end == END_FINAL ? FINAL : g.end == END_DECODE ? DECODE : g.end == END_PERSONS ? PERSONS : TO_NCHW;
         op.in = x;
         op.ext = HEAT;
-        op.n = n; op.c = c.out_channels;
+        op.n = n; op.ch = c.out_channels;
         p.push(op);
     }
     p.layout();
-    return UP_OK;
 }
-
-// ---- UniPose-LSTM (model/uniposeLSTM.py:67-138; the drop-in module unipose_amd/uniposeLSTM.py after checkpoint.load_folded) ----
-// STEP_FIRST / STEP_NEXT: the module's per-frame path (batch_frames = False) for iter == 0 (LSTM_0) resp. iter > 0 with the caller's
-// NCHW state; CLIP: its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True).  The evaluation entries run the same
-// launches and end differently: CLIP_KEYPOINTS decodes the NHWC output of conv5 (up_clip_heatmap_decode); CLIP_FLIP runs the whole
-// clip program twice, on the clip and on the mirrored clip (up_clip_nchw_to_nhwc_flip, up_clip_avgpool9s8_flip_fwd), each pass with
-// its own recurrent state, the first pass's heat-maps staying alive through the second, then up_flip_merge in place and the layout
-// pass; CLIP_FLIP_PREDS: the same, then up_clip_final_preds; CLIP_PREDS: one pass, then up_clip_final_preds.  STREAM_FIRST /
-// STREAM_NEXT: the step forms with the recurrent state in the caller's opaque NHWC buffer (whole padded rows copied in and out)
-// and up_heatmap_decode at the end; the NCHW heat-maps are optional.
-enum LstmForm { STEP_FIRST, STEP_NEXT, CLIP, CLIP_KEYPOINTS, CLIP_FLIP, CLIP_FLIP_PREDS, CLIP_PREDS, STREAM_FIRST, STREAM_NEXT, LSTM_FORMS };
 
 struct LstmPass {
     Ref y, cells, hides;       // conv5's output and the state tensors, frame-major (T * B, h, w, .)
     int h = 0, w = 0;
 };
 
-// One pass of a video program up to conv5: the trunk once on the T * B frame-major images (T = 1 in the step and stream forms), the
+// One pass of a video program up to conv5: the trunk once on the T * B frame-major images (T = 1 unless the input is a clip), the
 // recurrence frame by frame on rows of frame-major state tensors, the head once on the T * B hidden states.  Stacked gate
 // convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).  mirrored: the pass of the flip test.
-static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm form, bool mirrored) {
-    const bool clip = form >= CLIP && form <= CLIP_PREDS, next = form == STEP_NEXT || form == STREAM_NEXT;
+static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored) {
+    const bool clip = g.input == IN_CLIP;
     const int B = c.batch, T = clip ? c.frames : 1, n = T * B;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
     int h = c.height, w = c.width;
@@ -477,7 +461,7 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
         op.kind = !clip ? TO_NHWC : mirrored ? CLIP_TO_NHWC_FLIP : CLIP_TO_NHWC;
         op.out = x;
         op.ext = X;
-        op.n = B; op.a = T; op.c = 3;
+        op.n = B; op.frames = T; op.ch = 3;
         p.push(op);
     }
     Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true);
@@ -487,7 +471,7 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
     if (rup4(hc) == hc) {
         z.id = p.tensor(n, h, w, ldo);
         p.zero(z);
-        p.copy(heat, hc, z, ldo, 0, (long long)n * h * w, hc);
+        p.copy(heat, hc, z, ldo, 0, (int64_t)n * h * w, hc);
     }
     const int ldz = p.tensors[z.id].c;       // == ldo either way
     {
@@ -495,8 +479,8 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
         op.kind = !clip ? POOL : mirrored ? CLIP_POOL_FLIP : CLIP_POOL;
         op.out = z;
         op.ext = CENTER;
-        op.n = B; op.e = T;
-        op.a = c.height; op.b = c.width; op.c = hc;
+        op.n = B; op.frames = T;
+        op.src_h = c.height; op.src_w = c.width; op.coff = hc;
         p.push(op);
     }
     // the recurrence: cell / hide of all frames as rows of two frame-major tensors (the head reads the hidden states as one)
@@ -514,29 +498,29 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
         ct.elems += t * frame * ldo;
         ht.elems += t * frame * ldo;
         Op op;
-        op.n = B; op.c = cg;
+        op.n = B; op.ch = cg;
         op.out = ct; op.res = ht;
-        if (t == 0 && !next) {                // LSTM_0 (uniposeLSTM.py:9-24)
+        if (t == 0 && g.from == STATE_NONE) {    // LSTM_0 (uniposeLSTM.py:9-24)
             op.kind = LSTM0;
             op.in = p.conv("lstm_0", zt, B, h, w, ldz, cg, 3 * cg, 3, 1, 1, 1, 0, true);
         } else {                              // LSTM (uniposeLSTM.py:27-64): ONE convolution over cat(z, prev_hide)
             Ref ph, pc;
-            if (next) {
+            if (g.from != STATE_NONE) {
                 ph.id = p.tensor(B, h, w, ldo);
                 pc.id = p.tensor(B, h, w, ldo);
                 Op in;
-                if (form == STEP_NEXT) {      // the caller's NCHW state (unipose._state: ToNHWC, pad channels zero)
+                if (g.from == STATE_NCHW) {   // the caller's NCHW state (unipose._state: ToNHWC, pad channels zero)
                     in.kind = TO_NHWC;
-                    in.n = B; in.c = cg;
+                    in.n = B; in.ch = cg;
                     in.out = ph; in.ext = PREV_HIDE;
                     p.push(in);
                     in.out = pc; in.ext = PREV_CELL;
                     p.push(in);
                 } else {                      // the caller's state buffer: the plan's own NHWC rows, pad channels as the plan left them
                     in.kind = STATE_IN;
-                    in.out = ph; in.a = 0;
+                    in.out = ph; in.half = 0;
                     p.push(in);
-                    in.out = pc; in.a = 1;
+                    in.out = pc; in.half = 1;
                     p.push(in);
                 }
             } else {
@@ -547,8 +531,8 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
             }
             Ref zh;
             zh.id = p.tensor(B, h, w, ldz + ldo);
-            p.copy(zt, ldz, zh, ldz + ldo, 0, (long long)frame, ldz);
-            p.copy(ph, ldo, zh, ldz + ldo, ldz, (long long)frame, ldo);
+            p.copy(zt, ldz, zh, ldz + ldo, 0, (int64_t)frame, ldz);
+            p.copy(ph, ldo, zh, ldz + ldo, ldz, (int64_t)frame, ldo);
             op.kind = LSTM;
             op.in = p.conv("lstm", zh, B, h, w, ldz + ldo, ldz + ldo, 4 * cg, 3, 1, 1, 1, 0, true);
             op.aux = pc;
@@ -567,66 +551,60 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, LstmForm for
     return r;
 }
 
-static void build_lstm(Plan& p, const up_unipose_lstm_config& c, LstmForm form) {
-    const bool clip = form >= CLIP && form <= CLIP_PREDS, stream = form == STREAM_FIRST || form == STREAM_NEXT;
+static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g) {
+    const bool clip = g.input == IN_CLIP;
     const int B = c.batch, T = clip ? c.frames : 1;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
-    const LstmPass a = lstm_pass(p, c, form, false);
+    const LstmPass a = lstm_pass(p, c, g, false);
     Op op;
-    if (form == CLIP_FLIP || form == CLIP_FLIP_PREDS) {
-        const LstmPass m = lstm_pass(p, c, form, true);
+    if (g.flip) {
+        const LstmPass m = lstm_pass(p, c, g, true);
         op.kind = MERGE;                       // in place (NHWC): out == a with equal strides; both passes are frame-major
         op.in = a.y; op.aux = m.y; op.out = a.y;
-        op.n = T * B; op.c = hc;
+        op.n = T * B; op.ch = hc;
         p.push(op);
     }
-    if (form == CLIP_FLIP_PREDS || form == CLIP_PREDS || form == CLIP_KEYPOINTS) {
+    if (clip && g.end != END_HEAT) {           // a clip's joints: frame-major maps into batch-major results
         op = Op();
-        op.kind = form == CLIP_KEYPOINTS ? CLIP_DECODE : CLIP_FINAL;
+        op.kind = g.end == END_DECODE ? CLIP_DECODE : CLIP_FINAL;
         op.in = a.y;
-        op.n = B; op.a = T; op.c = hc;
+        op.n = B; op.frames = T; op.ch = hc;
         p.push(op);
-    }
-    if (form == CLIP_FLIP_PREDS || form == CLIP_PREDS) {
-        p.layout();
-        return;
     }
     const size_t frame = (size_t)B * a.h * a.w;
     Ref cl = a.cells, hl = a.hides;            // the state of the last frame
     cl.elems += (T - 1) * frame * ldo;
     hl.elems += (T - 1) * frame * ldo;
-    if (stream) {                              // the new state into the caller's buffer, then the joints
+    if (g.to == STATE_BUFFER) {                // the new state into the caller's buffer, then the joints
         op = Op();
         op.kind = STATE_OUT;
-        op.in = hl; op.a = 0;
+        op.in = hl; op.half = 0;
         p.push(op);
-        op.in = cl; op.a = 1;
+        op.in = cl; op.half = 1;
         p.push(op);
         op = Op();
         op.kind = DECODE;
         op.in = a.y;
-        op.n = B; op.c = hc;
+        op.n = B; op.ch = hc;
         p.push(op);
     }
-    if (form != CLIP_KEYPOINTS) {
+    if (g.end == END_HEAT || g.to == STATE_BUFFER) {
         op = Op();
-        op.kind = clip ? CLIP_TO_NCHW : TO_NCHW;     // TO_NCHW is skipped where the caller passes no tensor (the stream forms' heat)
+        op.kind = clip ? CLIP_TO_NCHW : TO_NCHW;     // TO_NCHW is skipped where the caller passes no tensor (a stream's heat)
         op.in = a.y;
         op.ext = HEAT;
-        op.n = B; op.a = T; op.c = hc;
+        op.n = B; op.frames = T; op.ch = hc;
         p.push(op);
     }
-    if (form == CLIP_FLIP || stream) {         // a flip program has two states and returns none; a stream's state is in its buffer
-        p.layout();
-        return;
+    if (g.to == STATE_NCHW) {
+        op = Op();
+        op.kind = TO_NCHW;
+        op.n = B; op.ch = cg;
+        op.in = cl; op.ext = CELL;
+        p.push(op);
+        op.in = hl; op.ext = HIDE;
+        p.push(op);
     }
-    op = Op();
-    op.kind = TO_NCHW;
-    op.n = B; op.c = cg;
-    op.in = cl; op.ext = CELL;
-    p.push(op);
-    op.in = hl; op.ext = HIDE;
-    p.push(op);
     p.layout();
 }
 
@@ -667,12 +645,16 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
     auto ptr = [&](const Ref& r) -> float* {
         return r.id < 0 ? nullptr : reinterpret_cast<float*>(ws + p.tensors[r.id].off) + r.elems;
     };
-    auto T_ = [&](const Ref& r) -> const Tensor& { return p.tensors[r.id]; };
+    static const Tensor none = {};
     for (const Op& op : p.ops) {
+        // the tensors the op names, and the batch stride of NHWC maps read in place
+        const Tensor& i = op.in.id < 0 ? none : p.tensors[op.in.id];
+        const Tensor& o = op.out.id < 0 ? none : p.tensors[op.out.id];
+        const int64_t image = (int64_t)i.h * i.w * i.c;
         int e = UP_OK;
         switch (op.kind) {
         case TO_NHWC:
-            e = up_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            e = up_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.ch, o.h, o.w, o.c, stream);
             break;
         case CONV: {
             const Conv& cv = p.convs[op.conv];
@@ -680,109 +662,236 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             memset(&ep, 0, sizeof(ep));
             ep.bias = cv.bias;
             ep.residual = ptr(op.res);
-            ep.ldr = op.res.id >= 0 ? T_(op.res).c : 0;
+            ep.ldr = op.res.id >= 0 ? p.tensors[op.res.id].c : 0;
             ep.relu = cv.relu;
             e = up_conv2d_fwd(&cv.d, ptr(op.in), cv.w_fwd, ptr(op.out), &ep, stream);
             break;
         }
         case MAXPOOL:
-            e = up_maxpool3s2_fwd(ptr(op.in), op.c, ptr(op.out), op.c, reinterpret_cast<uint8_t*>(ptr(op.res)), op.n, op.a, op.b, op.c,
-                                  (op.a - 1) / 2 + 1, (op.b - 1) / 2 + 1, stream);
+            e = up_maxpool3s2_fwd(ptr(op.in), i.c, ptr(op.out), o.c, reinterpret_cast<uint8_t*>(ptr(op.res)), op.n, i.h, i.w, i.c, o.h, o.w,
+                                  stream);
             break;
         case BILINEAR:
-            e = up_bilinear_fwd(ptr(op.in), op.c, ptr(op.out), op.c, op.n, op.a, op.b, op.c, op.e >> 16, op.e & 65535, stream);
+            e = up_bilinear_fwd(ptr(op.in), i.c, ptr(op.out), o.c, op.n, i.h, i.w, i.c, o.h, o.w, stream);
             break;
         case GAP:
-            e = up_gap_fwd(ptr(op.in), op.c, ptr(op.out), op.n, op.a, op.c, stream);
+            e = up_gap_fwd(ptr(op.in), i.c, ptr(op.out), op.n, i.h * i.w, i.c, stream);
             break;
         case COPY:
-            e = up_copy2d(ptr(op.in), op.a, ptr(op.out), op.b, op.e, op.c, stream);
+            e = up_copy2d(ptr(op.in), op.lds, ptr(op.out), op.ldd, op.rows, op.ch, stream);
             break;
         case ZERO:
-            if (hipMemsetAsync(ptr(op.out), 0, T_(op.out).bytes, as_stream(stream)) != hipSuccess) e = check_launch(what);
+            if (hipMemsetAsync(ptr(op.out), 0, o.bytes, as_stream(stream)) != hipSuccess) e = check_launch(what);
             break;
         case TO_NCHW:
-            if (io.out(op.ext))
-                e = up_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.out(op.ext), op.n, op.c, T_(op.in).h, T_(op.in).w, stream);
+            if (io.out(op.ext)) e = up_nhwc_to_nchw(ptr(op.in), i.c, io.out(op.ext), op.n, op.ch, i.h, i.w, stream);
             break;
         case DECODE:
-            e = up_heatmap_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c,
-                                  T_(op.in).h, T_(op.in).w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
+            e = up_heatmap_decode(ptr(op.in), image, 1, i.c, op.n, op.ch, i.h, i.w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
             break;
         case PERSONS:
-            e = up_persons_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c, T_(op.in).h,
-                                  T_(op.in).w, io.box_ch0, io.joint_ch0, io.njoints, io.max_persons, io.count, io.status, io.kpts, stream);
+            e = up_persons_decode(ptr(op.in), image, 1, i.c, op.n, op.ch, i.h, i.w, io.box_ch0, io.joint_ch0, io.njoints, io.max_persons,
+                                  io.count, io.status, io.kpts, stream);
             break;
         case TO_NHWC_FLIP:
-            e = up_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            e = up_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.ch, o.h, o.w, o.c, stream);
             break;
         case CROP:
-            e = up_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.c, io.frame_of, io.valid_hw, io.crop_inv, op.n,
-                                io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            e = up_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.ch, io.frame_of, io.valid_hw, io.crop_inv, op.n,
+                                io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), o.h, o.w, o.c, stream);
             break;
-        case MERGE: {
-            const Tensor& t = T_(op.in);
-            const int64_t sb = (int64_t)t.h * t.w * t.c;
+        case MERGE:
             if (op.out.id >= 0)
-                e = up_flip_merge(ptr(op.in), ptr(op.aux), sb, 1, t.c, op.n, op.c, t.h, t.w, io.perm, ptr(op.out), sb, 1, t.c, stream);
+                e = up_flip_merge(ptr(op.in), ptr(op.aux), image, 1, i.c, op.n, op.ch, i.h, i.w, io.perm, ptr(op.out), image, 1, i.c, stream);
             else
-                e = up_flip_merge(ptr(op.in), ptr(op.aux), sb, 1, t.c, op.n, op.c, t.h, t.w, io.perm, io.out(op.ext),
-                                  (int64_t)op.c * t.h * t.w, (int64_t)t.h * t.w, 1, stream);
+                e = up_flip_merge(ptr(op.in), ptr(op.aux), image, 1, i.c, op.n, op.ch, i.h, i.w, io.perm, io.out(op.ext),
+                                  (int64_t)op.ch * i.h * i.w, (int64_t)i.h * i.w, 1, stream);
             break;
-        }
         case FINAL:
-            e = up_final_preds(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.c, T_(op.in).h,
-                               T_(op.in).w, io.res0, io.res1, io.inv, io.preds, io.coords, io.maxvals, stream);
+            e = up_final_preds(ptr(op.in), image, 1, i.c, op.n, op.ch, i.h, i.w, io.res0, io.res1, io.inv, io.preds, io.coords, io.maxvals,
+                               stream);
             break;
         case POOL:
-            e = up_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.a, op.b, T_(op.out).h, T_(op.out).w, stream);
+            e = up_avgpool9s8_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case CLIP_POOL:
-            e = up_clip_avgpool9s8_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.e, op.a, op.b, T_(op.out).h, T_(op.out).w,
-                                       stream);
+            e = up_clip_avgpool9s8_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case LSTM0:
-            e = up_lstm0_fwd(ptr(op.in), T_(op.in).c, ptr(op.out), ptr(op.res), T_(op.out).c, (int64_t)op.n * T_(op.in).h * T_(op.in).w,
-                             op.c, stream);
+            e = up_lstm0_fwd(ptr(op.in), i.c, ptr(op.out), ptr(op.res), o.c, (int64_t)op.n * i.h * i.w, op.ch, stream);
             break;
         case LSTM:
-            e = up_lstm_fwd(ptr(op.in), T_(op.in).c, ptr(op.aux), T_(op.aux).c, ptr(op.out), ptr(op.res), T_(op.out).c,
-                            (int64_t)op.n * T_(op.in).h * T_(op.in).w, op.c, stream);
+            e = up_lstm_fwd(ptr(op.in), i.c, ptr(op.aux), p.tensors[op.aux.id].c, ptr(op.out), ptr(op.res), o.c, (int64_t)op.n * i.h * i.w,
+                            op.ch, stream);
             break;
         case CLIP_TO_NHWC:
-            e = up_clip_nchw_to_nhwc(io.x, ptr(op.out), op.n, op.a, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            e = up_clip_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
             break;
         case CLIP_TO_NCHW:
-            e = up_clip_nhwc_to_nchw(ptr(op.in), T_(op.in).c, io.heat, op.n, op.a, op.c, T_(op.in).h, T_(op.in).w, stream);
+            e = up_clip_nhwc_to_nchw(ptr(op.in), i.c, io.out(op.ext), op.n, op.frames, op.ch, i.h, i.w, stream);
             break;
         case CLIP_TO_NHWC_FLIP:
-            e = up_clip_nchw_to_nhwc_flip(io.x, ptr(op.out), op.n, op.a, op.c, T_(op.out).h, T_(op.out).w, T_(op.out).c, stream);
+            e = up_clip_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
             break;
         case CLIP_POOL_FLIP:
-            e = up_clip_avgpool9s8_flip_fwd(io.center, ptr(op.out), T_(op.out).c, op.c, op.n, op.e, op.a, op.b, T_(op.out).h,
-                                            T_(op.out).w, stream);
+            e = up_clip_avgpool9s8_flip_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case CLIP_DECODE:
-            e = up_clip_heatmap_decode(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.a, op.c,
-                                       T_(op.in).h, T_(op.in).w, io.dec_h, io.dec_w, io.idx, io.preds, io.maxvals, stream);
+            e = up_clip_heatmap_decode(ptr(op.in), image, 1, i.c, op.n, op.frames, op.ch, i.h, i.w, io.dec_h, io.dec_w, io.idx, io.preds,
+                                       io.maxvals, stream);
             break;
         case CLIP_FINAL:
-            e = up_clip_final_preds(ptr(op.in), (int64_t)T_(op.in).h * T_(op.in).w * T_(op.in).c, 1, T_(op.in).c, op.n, op.a, op.c,
-                                    T_(op.in).h, T_(op.in).w, io.res0, io.res1, io.inv, io.preds, io.coords, io.maxvals, stream);
+            e = up_clip_final_preds(ptr(op.in), image, 1, i.c, op.n, op.frames, op.ch, i.h, i.w, io.res0, io.res1, io.inv, io.preds,
+                                    io.coords, io.maxvals, stream);
             break;
-        case STATE_IN: {                       // whole padded rows: the pad channels stay the zeros the plan wrote
-            const Tensor& t = T_(op.out);
-            e = up_copy2d(io.state + op.a * io.state_half, t.c, ptr(op.out), t.c, (int64_t)t.n * t.h * t.w, t.c, stream);
+        case STATE_IN:                         // whole padded rows: the pad channels stay the zeros the plan wrote
+            e = up_copy2d(io.state + op.half * io.state_half, o.c, ptr(op.out), o.c, (int64_t)o.n * o.h * o.w, o.c, stream);
             break;
-        }
-        case STATE_OUT: {
-            const Tensor& t = T_(op.in);
-            e = up_copy2d(ptr(op.in), t.c, io.state + op.a * io.state_half, t.c, (int64_t)t.n * t.h * t.w, t.c, stream);
+        case STATE_OUT:
+            e = up_copy2d(ptr(op.in), i.c, io.state + op.half * io.state_half, i.c, (int64_t)i.n * i.h * i.w, i.c, stream);
             break;
-        }
         }
         if (e) return e;
     }
+    return UP_OK;
+}
+
+// ---- the weights of a plan --------------------------------------------------------------------------------------------------------
+// Stored once per distinct parameter and shared by every program, and within one (wasp.conv2 is applied twice).  The ConvLSTM
+// gate convolutions of the video plan are set part by part under their state_dict names and stacked by the plan
+// (modules.LSTM_0.forward / modules.LSTM.stacked): along the output channels, the x / h parts' input channels padded to rup4,
+// each gate bias the fp32 sum bx + bh.
+struct Store {                 // one packed forward weight image (+ bias)
+    std::string name;          // a state_dict prefix, or "lstm_0" / "lstm" for the stacked gate convolutions
+    up_conv_desc d;            // descriptor of its first use (the packed image depends on K, C, Cp, R, S only)
+    bool has_bias = false;
+    float* w_fwd = nullptr;
+    float* bias = nullptr;
+    int parts = 0;             // stacked: 3 (g, i, o) or 8 (gx, ix, ox, fx, gh, ih, oh, fh), else 0
+    float* stage_w = nullptr;  // stacked: the OIHW image the parts are copied into (pad channels zero)
+    float* stage_b = nullptr;  // stacked: [parts][cg] the parts' biases
+    bool staged = false;       // stage_w zeroed (on the stream of the first set_conv)
+};
+struct Entry {                 // one listed convolution
+    std::string name;
+    int32_t oihw[4];
+    bool has_bias;
+    int store;
+    int part = -1;             // >= 0: slot of a stacked gate weight
+    bool set = false;
+};
+struct Weights {
+    std::vector<Store> stores;
+    std::vector<Entry> entries;
+
+    int store_of(const std::string& name) const {
+        for (size_t s = 0; s < stores.size(); ++s)
+            if (stores[s].name == name) return (int)s;
+        return -1;
+    }
+    // One store per distinct name of the programs, in device memory, and every convolution bound to its own.  cg: channels of one
+    // gate of the stacked convolutions.  false: out of device memory (release() takes what was allocated).
+    bool bind(Plan* progs, size_t count, int cg) {
+        for (size_t f = 0; f < count; ++f)
+            for (const Conv& cv : progs[f].convs) {
+                if (store_of(cv.name) >= 0) continue;
+                Store st;
+                st.name = cv.name;
+                st.d = cv.d;
+                st.has_bias = cv.has_bias;
+                st.parts = cv.name == "lstm_0" ? 3 : cv.name == "lstm" ? 8 : 0;
+                stores.push_back(st);
+            }
+        bool ok = true;
+        for (Store& st : stores) {
+            st.w_fwd = static_cast<float*>(dev_alloc((size_t)st.d.K * st.d.R * st.d.S * st.d.Cp * sizeof(float)));
+            if (st.has_bias) st.bias = static_cast<float*>(dev_alloc((size_t)st.d.K * sizeof(float)));
+            ok = ok && st.w_fwd && (!st.has_bias || st.bias);
+            if (st.parts) {
+                st.stage_w = static_cast<float*>(dev_alloc((size_t)st.d.K * st.d.C * st.d.R * st.d.S * sizeof(float)));
+                st.stage_b = static_cast<float*>(dev_alloc((size_t)st.parts * cg * sizeof(float)));
+                ok = ok && st.stage_w && st.stage_b;
+            }
+        }
+        for (size_t f = 0; f < count; ++f)
+            for (Conv& cv : progs[f].convs) {
+                const Store& st = stores[store_of(cv.name)];
+                cv.w_fwd = st.w_fwd;
+                cv.bias = st.bias;
+            }
+        return ok;
+    }
+    void list(const std::string& name, int store, int part, int k, int c, int r, bool bias) {
+        Entry e;
+        e.name = name;
+        e.oihw[0] = k; e.oihw[1] = c; e.oihw[2] = r; e.oihw[3] = r;
+        e.has_bias = bias;
+        e.store = store;
+        e.part = part;
+        entries.push_back(e);
+    }
+    void release() {
+        for (Store& st : stores) {
+            dev_free(st.w_fwd);
+            dev_free(st.bias);
+            dev_free(st.stage_w);
+            dev_free(st.stage_b);
+        }
+    }
+};
+
+// The listing both plans answer with (`w` is NULL where the plan is); `what` names the C function in the refusal.
+static int num_convs(const Weights* w) { return w ? (int)w->entries.size() : UP_ERR_INVALID; }
+static const char* conv_name(const Weights* w, int i) { return (w && i >= 0 && i < (int)w->entries.size()) ? w->entries[i].name.c_str() : ""; }
+static int conv_shape(const Weights* w, int i, int32_t* oihw, int32_t* has_bias, const char* what) {
+    UP_REQUIRE(w && oihw && i >= 0 && i < (int)w->entries.size(), UP_ERR_INVALID, "%s: bad argument", what);
+    const Entry& e = w->entries[i];
+    memcpy(oihw, e.oihw, sizeof(e.oihw));
+    if (has_bias) *has_bias = e.has_bias ? 1 : 0;
+    return UP_OK;
+}
+static int set_conv_check(const Weights* w, int i, const float* w_oihw, const float* bias, const char* what) {
+    UP_REQUIRE(w && w_oihw && i >= 0 && i < (int)w->entries.size(), UP_ERR_INVALID, "%s: bad argument", what);
+    const Entry& en = w->entries[i];
+    UP_REQUIRE((bias != nullptr) == en.has_bias, UP_ERR_INVALID, "%s: %s %s a bias (folded network)", what, en.name.c_str(),
+               en.has_bias ? "needs" : "has no");
+    return UP_OK;
+}
+// an entry that is a whole parameter: packed into its store; every listing of the name is set with it
+static int set_conv_whole(Weights& w, int i, const float* w_oihw, const float* bias, void* stream) {
+    const Entry& en = w.entries[i];
+    const Store& st = w.stores[en.store];
+    if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) return e;
+    if (bias)
+        if (int e = up_copy2d(bias, st.d.K, st.bias, st.d.K, 1, st.d.K, stream)) return e;
+    for (Entry& other : w.entries)
+        if (other.name == en.name) other.set = true;
+    return UP_OK;
+}
+
+// ---- one call -----------------------------------------------------------------------------------------------------------------------
+// Weights set, a workspace of `need` bytes, then the launches.  setter: the function the "never set" refusal points to;
+// ws_code: what a too-small or misaligned workspace returns (the two plans differ).
+static int launch(const Weights& w, const char* setter, const Plan& prog, size_t need, int ws_code, const Io& io, void* workspace,
+                  size_t ws_bytes, void* stream, const char* what) {
+    for (const Entry& e : w.entries)
+        UP_REQUIRE(e.set, UP_ERR_INVALID, "%s: weights of %s were never set (%s)", what, e.name.c_str(), setter);
+    UP_REQUIRE(ws_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, ws_code,
+               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, need, ws_bytes);
+    return run(prog, io, static_cast<unsigned char*>(workspace), stream, what);
+}
+// the channel permutation of a flip-test call over C `noun` channels: refused before the first launch of the program
+static int perm_ok(int C, const char* noun, const int32_t* perm, const char* what) {
+    UP_REQUIRE(C <= 256, UP_ERR_UNSUPPORTED, "%s: %d %s channels (up_flip_merge takes up to 256)", what, C, noun);
+    for (int j = 0; j < C; ++j)
+        UP_REQUIRE(perm[j] >= 0 && perm[j] < C, UP_ERR_INVALID, "%s: perm[%d] = %d outside 0..%d", what, j, (int)perm[j], C - 1);
+    return UP_OK;
+}
+// the grid of a decode: the heat-maps' own (three ceil-halvings of the H x W input) or the input's
+static int grid_ok(int out_h, int out_w, int H, int W, const char* what) {
+    const int h = (H - 1) / 8 + 1, w = (W - 1) / 8 + 1;
+    UP_REQUIRE((out_h == h && out_w == w) || (out_h == H && out_w == W), UP_ERR_INVALID,
+               "%s: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", what, out_h, out_w, h, w, H, W);
     return UP_OK;
 }
 
@@ -792,18 +901,15 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
 using namespace up;
 using up::plan::Plan;
 
+// ---- the image plan -----------------------------------------------------------------------------------------------------------------
+static const size_t IMAGE_FORMS = sizeof(plan::IMAGE_PROGRAMS) / sizeof(plan::IMAGE_PROGRAMS[0]);
+
 struct up_unipose_plan {
     up_unipose_config cfg;
-    Plan p;                    // HEAT_MAPS; its convolutions are the listed ones and own the weight store
-    Plan up, kp, ps;           // UPSAMPLED, KEYPOINTS, PERSONS_FORM: the same trunk, so the same convolutions in the same order
-    Plan fh, fp, pr;           // FLIP_HEAT, FLIP_PREDS (the trunk twice: every convolution name twice), PREDS
-    Plan rh, rfh, rfp, rpr;    // FRAME_HEAT, FRAME_FLIP_HEAT, FRAME_FLIP_PREDS, FRAME_PREDS: their needs are reported per program only
-    size_t ws_bytes = 0;       // the largest of the first four
-    size_t flip_ws_bytes = 0;  // the largest of the next three
-    Plan* prog(int form) {
-        Plan* const all[up::plan::IMAGE_FORMS] = {&p, &up, &kp, &ps, &fh, &fp, &pr, &rh, &rfh, &rfp, &rpr};
-        return all[form];
-    }
+    Plan prog[IMAGE_FORMS];    // as IMAGE_PROGRAMS lists them
+    plan::Weights w;           // the listed convolutions are those of program 0: the 116 of the forward, wasp.conv2 twice
+    size_t ws_bytes = 0;       // the largest of the programs that count toward it, and ...
+    size_t flip_ws_bytes = 0;  // ... toward the flip test's
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
@@ -815,83 +921,39 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
-    for (int f = 0; f < plan::IMAGE_FORMS; ++f) {
-        if (int e = up::plan::build(*pl->prog(f), pl->cfg, static_cast<plan::ImageForm>(f))) {
-            delete pl;
-            return e;
-        }
-        if (f >= plan::FRAME_HEAT) continue;
-        size_t& need = f < plan::FLIP_HEAT ? pl->ws_bytes : pl->flip_ws_bytes;
-        need = std::max(need, pl->prog(f)->ws_bytes);
+    for (size_t f = 0; f < IMAGE_FORMS; ++f) {
+        const plan::Program& g = plan::IMAGE_PROGRAMS[f];
+        plan::build(pl->prog[f], pl->cfg, g);
+        if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
+        if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
     }
-    // plan-owned device memory: one forward weight image (+ bias) per DISTINCT parameter (wasp.conv2 is applied twice)
-    for (size_t i = 0; i < pl->p.convs.size(); ++i) {
-        plan::Conv& cv = pl->p.convs[i];
-        for (size_t j = 0; j < i; ++j)
-            if (pl->p.convs[j].name == cv.name) {
-                cv.w_fwd = pl->p.convs[j].w_fwd;
-                cv.bias = pl->p.convs[j].bias;
-            }
-        if (cv.w_fwd) continue;
-        const size_t nf = (size_t)cv.d.K * cv.d.R * cv.d.S * cv.d.Cp;
-        cv.w_fwd = static_cast<float*>(plan::dev_alloc(nf * sizeof(float)));
-        if (cv.has_bias) cv.bias = static_cast<float*>(plan::dev_alloc((size_t)cv.d.K * sizeof(float)));
-        if (!cv.w_fwd || (cv.has_bias && !cv.bias)) {
-            up_unipose_plan_destroy(pl);
-            UP_REQUIRE(false, UP_ERR_INVALID, "unipose_plan_create: out of device memory");
-        }
+    const bool ok = pl->w.bind(pl->prog, IMAGE_FORMS, 0);
+    for (const plan::Conv& cv : pl->prog[0].convs) pl->w.list(cv.name, pl->w.store_of(cv.name), -1, cv.d.K, cv.d.C, cv.d.R, cv.has_bias);
+    if (!ok) {
+        up_unipose_plan_destroy(pl);
+        UP_REQUIRE(false, UP_ERR_INVALID, "unipose_plan_create: out of device memory");
     }
-    // the other programs share the store by NAME (the flip programs run the trunk twice)
-    for (int f = 1; f < plan::IMAGE_FORMS; ++f)
-        for (plan::Conv& cv : pl->prog(f)->convs)
-            for (const plan::Conv& own : pl->p.convs)
-                if (own.name == cv.name) {
-                    cv.w_fwd = own.w_fwd;
-                    cv.bias = own.bias;
-                    break;
-                }
     *out = pl;
     return UP_OK;
 }
 
 extern "C" void up_unipose_plan_destroy(up_unipose_plan* pl) {
     if (!pl) return;
-    for (size_t i = 0; i < pl->p.convs.size(); ++i) {
-        plan::Conv& cv = pl->p.convs[i];
-        bool shared = false;
-        for (size_t j = 0; j < i; ++j) shared = shared || pl->p.convs[j].name == cv.name;
-        if (shared) continue;
-        plan::dev_free(cv.w_fwd);
-        plan::dev_free(cv.bias);
-    }
+    pl->w.release();
     delete pl;
 }
 
-extern "C" int up_unipose_plan_num_convs(const up_unipose_plan* pl) { return pl ? (int)pl->p.convs.size() : UP_ERR_INVALID; }
+extern "C" int up_unipose_plan_num_convs(const up_unipose_plan* pl) { return plan::num_convs(pl ? &pl->w : nullptr); }
 
-extern "C" const char* up_unipose_plan_conv_name(const up_unipose_plan* pl, int i) {
-    return (pl && i >= 0 && i < (int)pl->p.convs.size()) ? pl->p.convs[i].name.c_str() : "";
-}
+extern "C" const char* up_unipose_plan_conv_name(const up_unipose_plan* pl, int i) { return plan::conv_name(pl ? &pl->w : nullptr, i); }
 
 extern "C" int up_unipose_plan_conv_shape(const up_unipose_plan* pl, int i, int32_t* oihw, int32_t* has_bias) {
-    UP_REQUIRE(pl && oihw && i >= 0 && i < (int)pl->p.convs.size(), UP_ERR_INVALID, "unipose_plan_conv_shape: bad argument");
-    const plan::Conv& cv = pl->p.convs[i];
-    oihw[0] = cv.d.K; oihw[1] = cv.d.C; oihw[2] = cv.d.R; oihw[3] = cv.d.S;
-    if (has_bias) *has_bias = cv.has_bias ? 1 : 0;
-    return UP_OK;
+    return plan::conv_shape(pl ? &pl->w : nullptr, i, oihw, has_bias, "unipose_plan_conv_shape");
 }
 
 extern "C" int up_unipose_plan_set_conv(up_unipose_plan* pl, int i, const float* w_oihw, const float* bias, void* stream) {
-    UP_REQUIRE(pl && w_oihw && i >= 0 && i < (int)pl->p.convs.size(), UP_ERR_INVALID, "unipose_plan_set_conv: bad argument");
-    plan::Conv& cv = pl->p.convs[i];
-    UP_REQUIRE((bias != nullptr) == cv.has_bias, UP_ERR_INVALID, "unipose_plan_set_conv: %s %s a bias (folded network)", cv.name.c_str(),
-               cv.has_bias ? "needs" : "has no");
-    if (int e = up_pack_weights(&cv.d, w_oihw, cv.w_fwd, nullptr, stream)) return e;
-    if (bias)
-        if (int e = up_copy2d(bias, cv.d.K, cv.bias, cv.d.K, 1, cv.d.K, stream)) return e;
-    for (plan::Conv& other : pl->p.convs)
-        if (other.name == cv.name) other.set = true;
-    return UP_OK;
+    if (int e = plan::set_conv_check(pl ? &pl->w : nullptr, i, w_oihw, bias, "unipose_plan_set_conv")) return e;
+    return plan::set_conv_whole(pl->w, i, w_oihw, bias, stream);
 }
 
 extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return pl ? pl->ws_bytes : 0; }
@@ -899,54 +961,38 @@ extern "C" size_t up_unipose_plan_workspace(const up_unipose_plan* pl) { return 
 extern "C" size_t up_unipose_plan_flip_workspace(const up_unipose_plan* pl) { return pl ? pl->flip_ws_bytes : 0; }
 
 extern "C" size_t up_unipose_plan_program_workspace(const up_unipose_plan* pl, int program) {
-    if (!pl) return 0;
-    int form = program;
-    if (program >= UP_PROGRAM_FROM_FRAMES) {     // the program that starts from source frames, named by the one it otherwise equals
-        const int k = program - UP_PROGRAM_FROM_FRAMES;
-        form = k == plan::HEAT_MAPS ? plan::FRAME_HEAT : k == plan::FLIP_HEAT ? plan::FRAME_FLIP_HEAT
-               : k == plan::FLIP_PREDS ? plan::FRAME_FLIP_PREDS : k == plan::PREDS ? plan::FRAME_PREDS : -1;
-    } else if (program >= plan::FRAME_HEAT) {
-        form = -1;
-    }
-    return form >= 0 ? const_cast<up_unipose_plan*>(pl)->prog(form)->ws_bytes : 0;
+    return pl ? plan::program_workspace(plan::IMAGE_PROGRAMS, pl->prog, program) : 0;
 }
 
-static int image_ready(const up_unipose_plan* pl, const Plan& prog, const void* workspace, size_t ws_bytes, const char* what) {
-    for (const plan::Conv& cv : pl->p.convs)
-        UP_REQUIRE(cv.set, UP_ERR_INVALID, "%s: weights of %s were never set (up_unipose_plan_set_conv)", what, cv.name.c_str());
-    UP_REQUIRE(ws_bytes >= prog.ws_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_INVALID,
-               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, prog.ws_bytes, ws_bytes);
-    return UP_OK;
+// the program of an entry's arguments, ready and run: a too-small workspace is UP_ERR_INVALID from this plan
+static int launch(up_unipose_plan* pl, plan::Input input, bool flip, plan::Ending end, const plan::Io& io, void* workspace, size_t ws_bytes,
+                  void* stream, const char* what) {
+    const Plan& prog = pl->prog[plan::find(plan::IMAGE_PROGRAMS, input, flip, end)];
+    return plan::launch(pl->w, "up_unipose_plan_set_conv", prog, prog.ws_bytes, UP_ERR_INVALID, io, workspace, ws_bytes, stream, what);
 }
 
 extern "C" int up_unipose_forward(up_unipose_plan* pl, const float* x_nchw, float* heat_nchw, void* workspace, size_t ws_bytes,
                                   void* stream) {
     UP_REQUIRE(pl && x_nchw && heat_nchw && workspace, UP_ERR_INVALID, "unipose_forward: null argument");
-    if (int e = image_ready(pl, pl->p, workspace, ws_bytes, "unipose_forward")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.heat = heat_nchw;
-    return plan::run(pl->p, io, static_cast<unsigned char*>(workspace), stream, "unipose_forward");
+    return launch(pl, plan::IN_NCHW, false, plan::END_HEAT, io, workspace, ws_bytes, stream, "unipose_forward");
 }
 
 extern "C" int up_unipose_forward_upsampled(up_unipose_plan* pl, const float* x_nchw, float* heat_nchw, void* workspace,
                                             size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x_nchw && heat_nchw && workspace, UP_ERR_INVALID, "unipose_forward_upsampled: null argument");
-    if (int e = image_ready(pl, pl->up, workspace, ws_bytes, "unipose_forward_upsampled")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.heat = heat_nchw;
-    return plan::run(pl->up, io, static_cast<unsigned char*>(workspace), stream, "unipose_forward_upsampled");
+    return launch(pl, plan::IN_NCHW, false, plan::END_UPSAMPLED, io, workspace, ws_bytes, stream, "unipose_forward_upsampled");
 }
 
 extern "C" int up_unipose_keypoints(up_unipose_plan* pl, const float* x_nchw, int out_h, int out_w, int32_t* idx, float* preds_xy,
                                     float* maxvals, void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_keypoints: null argument");
-    const plan::Tensor& heat = pl->kp.tensors[pl->kp.ops.back().in.id];
-    UP_REQUIRE((out_h == heat.h && out_w == heat.w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
-               "unipose_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h, out_w,
-               heat.h, heat.w, pl->cfg.height, pl->cfg.width);
-    if (int e = image_ready(pl, pl->kp, workspace, ws_bytes, "unipose_keypoints")) return e;
+    if (int e = plan::grid_ok(out_h, out_w, pl->cfg.height, pl->cfg.width, "unipose_keypoints")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.dec_h = out_h;
@@ -954,7 +1000,7 @@ extern "C" int up_unipose_keypoints(up_unipose_plan* pl, const float* x_nchw, in
     io.idx = idx;
     io.preds = preds_xy;
     io.maxvals = maxvals;
-    return plan::run(pl->kp, io, static_cast<unsigned char*>(workspace), stream, "unipose_keypoints");
+    return launch(pl, plan::IN_NCHW, false, plan::END_DECODE, io, workspace, ws_bytes, stream, "unipose_keypoints");
 }
 
 extern "C" int up_unipose_persons(up_unipose_plan* pl, const float* x_nchw, int box_ch0, int joint_ch0, int njoints, int max_persons,
@@ -970,7 +1016,6 @@ extern "C" int up_unipose_persons(up_unipose_plan* pl, const float* x_nchw, int 
     UP_REQUIRE((int64_t)pl->cfg.batch * max_persons * (njoints + 5) * 2 <= INT32_MAX, UP_ERR_INVALID,
                "unipose_persons: %d persons of %d rows for %d samples: an index beyond the int32 range", max_persons, njoints + 5,
                pl->cfg.batch);
-    if (int e = image_ready(pl, pl->ps, workspace, ws_bytes, "unipose_persons")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.box_ch0 = box_ch0;
@@ -980,28 +1025,18 @@ extern "C" int up_unipose_persons(up_unipose_plan* pl, const float* x_nchw, int 
     io.count = count;
     io.status = status;
     io.kpts = kpts;
-    return plan::run(pl->ps, io, static_cast<unsigned char*>(workspace), stream, "unipose_persons");
-}
-
-// the channel permutation of a flip-test call: refused here, before the first launch of the program
-static int perm_ok(const up_unipose_plan* pl, const int32_t* perm, const char* what) {
-    const int C = pl->cfg.out_channels;
-    UP_REQUIRE(C <= 256, UP_ERR_UNSUPPORTED, "%s: %d output channels (up_flip_merge takes up to 256)", what, C);
-    for (int j = 0; j < C; ++j)
-        UP_REQUIRE(perm[j] >= 0 && perm[j] < C, UP_ERR_INVALID, "%s: perm[%d] = %d outside 0..%d", what, j, (int)perm[j], C - 1);
-    return UP_OK;
+    return launch(pl, plan::IN_NCHW, false, plan::END_PERSONS, io, workspace, ws_bytes, stream, "unipose_persons");
 }
 
 extern "C" int up_unipose_flip_forward(up_unipose_plan* pl, const float* x_nchw, const int32_t* perm_host, float* heat_nchw,
                                        void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x_nchw && perm_host && heat_nchw && workspace, UP_ERR_INVALID, "unipose_flip_forward: null argument");
-    if (int e = perm_ok(pl, perm_host, "unipose_flip_forward")) return e;
-    if (int e = image_ready(pl, pl->fh, workspace, ws_bytes, "unipose_flip_forward")) return e;
+    if (int e = plan::perm_ok(pl->cfg.out_channels, "output", perm_host, "unipose_flip_forward")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.perm = perm_host;
     io.heat = heat_nchw;
-    return plan::run(pl->fh, io, static_cast<unsigned char*>(workspace), stream, "unipose_flip_forward");
+    return launch(pl, plan::IN_NCHW, true, plan::END_HEAT, io, workspace, ws_bytes, stream, "unipose_flip_forward");
 }
 
 extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, const int32_t* perm_host, const double* inv, int res0,
@@ -1010,9 +1045,7 @@ extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, 
     UP_REQUIRE(pl && x_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_final_preds: null argument");
     UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_final_preds: res %d, %d", res0, res1);
     if (perm_host)
-        if (int e = perm_ok(pl, perm_host, "unipose_final_preds")) return e;
-    const Plan& prog = perm_host ? pl->fp : pl->pr;
-    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_final_preds")) return e;
+        if (int e = plan::perm_ok(pl->cfg.out_channels, "output", perm_host, "unipose_final_preds")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.perm = perm_host;
@@ -1022,11 +1055,11 @@ extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, 
     io.preds = preds_xy;
     io.coords = coords_xy;
     io.maxvals = maxvals;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_final_preds");
+    return launch(pl, plan::IN_NCHW, perm_host != nullptr, plan::END_FINAL, io, workspace, ws_bytes, stream, "unipose_final_preds");
 }
 
-// From source frames (ABI 10 additions): the crop of up_crop_to_nhwc in front of the same programs.  Its own refusals (source type,
-// sizes, frame_of == NULL with F != batch, std) come from its wrapper, which is the program's first launch: nothing runs before it.
+// From source frames: the crop of up_crop_to_nhwc in front of the same programs.  Its own refusals (source type, sizes,
+// frame_of == NULL with F != batch, std) come from its wrapper, which is the program's first launch: nothing runs before it.
 static int frame_io(const up_unipose_plan* pl, plan::Io& io, const void* src_hwc, int src_type, int F, int Hs, int Ws,
                     const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border, float mean, float stdv,
                     const char* what) {
@@ -1059,12 +1092,10 @@ extern "C" int up_unipose_frame_heatmaps(up_unipose_plan* pl, const void* src_hw
     if (int e = frame_io(pl, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, "unipose_frame_heatmaps"))
         return e;
     if (perm_host)
-        if (int e = perm_ok(pl, perm_host, "unipose_frame_heatmaps")) return e;
-    const Plan& prog = perm_host ? pl->rfh : pl->rh;
-    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_frame_heatmaps")) return e;
+        if (int e = plan::perm_ok(pl->cfg.out_channels, "output", perm_host, "unipose_frame_heatmaps")) return e;
     io.perm = perm_host;
     io.heat = heat_nchw;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_frame_heatmaps");
+    return launch(pl, plan::IN_FRAMES, perm_host != nullptr, plan::END_HEAT, io, workspace, ws_bytes, stream, "unipose_frame_heatmaps");
 }
 
 extern "C" int up_unipose_frame_final_preds(up_unipose_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
@@ -1079,9 +1110,7 @@ extern "C" int up_unipose_frame_final_preds(up_unipose_plan* pl, const void* src
                          "unipose_frame_final_preds"))
         return e;
     if (perm_host)
-        if (int e = perm_ok(pl, perm_host, "unipose_frame_final_preds")) return e;
-    const Plan& prog = perm_host ? pl->rfp : pl->rpr;
-    if (int e = image_ready(pl, prog, workspace, ws_bytes, "unipose_frame_final_preds")) return e;
+        if (int e = plan::perm_ok(pl->cfg.out_channels, "output", perm_host, "unipose_frame_final_preds")) return e;
     io.perm = perm_host;
     io.inv = inv;
     io.res0 = res0;
@@ -1089,47 +1118,18 @@ extern "C" int up_unipose_frame_final_preds(up_unipose_plan* pl, const void* src
     io.preds = preds_xy;
     io.coords = coords_xy;
     io.maxvals = maxvals;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_frame_final_preds");
+    return launch(pl, plan::IN_FRAMES, perm_host != nullptr, plan::END_FINAL, io, workspace, ws_bytes, stream, "unipose_frame_final_preds");
 }
 
-// ---- UniPose-LSTM (ABI 10 additions) ------------------------------------------------------------------------------------------
-// All programs (LstmForm) share one weight store: the per-frame step for the first frame (LSTM_0) and for a later one (LSTM over
-// the caller's state), the whole clip, and the evaluation entries over the same launches.  Weights are stored once per distinct parameter; the ConvLSTM gate convolutions are set
-// part by part under their state_dict names and stacked by the plan (modules.LSTM_0.forward / modules.LSTM.stacked): along the
-// output channels, the x / h parts' input channels padded to rup4, each gate bias the fp32 sum bx + bh.
-namespace up {
-namespace plan {
-
-struct Store {                 // one packed forward weight image (+ bias)
-    std::string name;          // a state_dict prefix, or "lstm_0" / "lstm" for the stacked gate convolutions
-    up_conv_desc d;            // descriptor of its first use (the packed image depends on K, C, Cp, R, S only)
-    bool has_bias = false;
-    float* w_fwd = nullptr;
-    float* bias = nullptr;
-    int parts = 0;             // stacked: 3 (g, i, o) or 8 (gx, ix, ox, fx, gh, ih, oh, fh), else 0
-    float* stage_w = nullptr;  // stacked: the OIHW image the parts are copied into (pad channels zero)
-    float* stage_b = nullptr;  // stacked: [parts][cg] the parts' biases
-    bool staged = false;       // stage_w zeroed (on the stream of the first set_conv)
-};
-struct Entry {                 // one listed convolution
-    std::string name;
-    int32_t oihw[4];
-    bool has_bias;
-    int store;
-    int part = -1;             // >= 0: slot of a stacked gate weight
-    bool set = false;
-};
-
-}  // namespace plan
-}  // namespace up
+// ---- the video plan -----------------------------------------------------------------------------------------------------------------
+static const size_t LSTM_FORMS = sizeof(plan::LSTM_PROGRAMS) / sizeof(plan::LSTM_PROGRAMS[0]);
 
 struct up_unipose_lstm_plan {
     up_unipose_lstm_config cfg;
-    Plan prog[plan::LSTM_FORMS];
-    std::vector<plan::Store> stores;
-    std::vector<plan::Entry> entries;
+    Plan prog[LSTM_FORMS];     // as LSTM_PROGRAMS lists them
+    plan::Weights w;
     size_t ws_bytes = 0;       // the largest of the programs without the flip test
-    size_t flip_ws_bytes = 0;  // the largest of CLIP_FLIP and CLIP_FLIP_PREDS
+    size_t flip_ws_bytes = 0;  // the largest of those with it
     size_t state_half = 0;     // elements of one (B, h, w, rup4(K + 2)) state tensor in a stream's buffer, a multiple of 64
 };
 
@@ -1150,71 +1150,28 @@ extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up
     up_unipose_lstm_plan* pl = new (std::nothrow) up_unipose_lstm_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_lstm_plan_create: out of host memory");
     pl->cfg = *cfg;
-    for (int f = 0; f < plan::LSTM_FORMS; ++f) {
-        plan::build_lstm(pl->prog[f], pl->cfg, static_cast<plan::LstmForm>(f));
-        size_t& need = f == plan::CLIP_FLIP || f == plan::CLIP_FLIP_PREDS ? pl->flip_ws_bytes : pl->ws_bytes;
-        need = std::max(need, pl->prog[f].ws_bytes);
+    for (size_t f = 0; f < LSTM_FORMS; ++f) {
+        const plan::Program& g = plan::LSTM_PROGRAMS[f];
+        plan::build_lstm(pl->prog[f], pl->cfg, g);
+        if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
+        if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
+        for (const plan::Op& op : pl->prog[f].ops)       // the hidden state STATE_OUT copies: its tensor's padded size
+            if (op.kind == plan::STATE_OUT) pl->state_half = pl->prog[f].tensors[op.in.id].bytes / sizeof(float);
     }
-    {   // the hidden state STATE_OUT copies: its tensor's padded size
-        const Plan& sp = pl->prog[plan::STREAM_FIRST];
-        for (const plan::Op& op : sp.ops)
-            if (op.kind == plan::STATE_OUT) pl->state_half = sp.tensors[op.in.id].bytes / sizeof(float);
-    }
-    // the weight store: every distinct name of the three programs
-    auto store_of = [&](const std::string& name) {
-        for (size_t s = 0; s < pl->stores.size(); ++s)
-            if (pl->stores[s].name == name) return (int)s;
-        return -1;
-    };
-    for (Plan& p : pl->prog)
-        for (const plan::Conv& cv : p.convs) {
-            if (store_of(cv.name) >= 0) continue;
-            plan::Store st;
-            st.name = cv.name;
-            st.d = cv.d;
-            st.has_bias = cv.has_bias;
-            st.parts = cv.name == "lstm_0" ? 3 : cv.name == "lstm" ? 8 : 0;
-            pl->stores.push_back(st);
-        }
     const int cg = cfg->num_classes + 2;
-    bool ok = true;
-    for (plan::Store& st : pl->stores) {
-        st.w_fwd = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * st.d.R * st.d.S * st.d.Cp * sizeof(float)));
-        if (st.has_bias) st.bias = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * sizeof(float)));
-        ok = ok && st.w_fwd && (!st.has_bias || st.bias);
-        if (st.parts) {
-            st.stage_w = static_cast<float*>(plan::dev_alloc((size_t)st.d.K * st.d.C * st.d.R * st.d.S * sizeof(float)));
-            st.stage_b = static_cast<float*>(plan::dev_alloc((size_t)st.parts * cg * sizeof(float)));
-            ok = ok && st.stage_w && st.stage_b;
-        }
-    }
-    for (Plan& p : pl->prog)
-        for (plan::Conv& cv : p.convs) {
-            const plan::Store& st = pl->stores[store_of(cv.name)];
-            cv.w_fwd = st.w_fwd;
-            cv.bias = st.bias;
-        }
+    const bool ok = pl->w.bind(pl->prog, LSTM_FORMS, cg);
     // the listed convolutions: the trunk in program order (wasp.conv2 twice, like the image plan), the gate parts, the head
     static const char* const gates0[3] = {"g", "i", "o"};
     static const char* const gates[8] = {"gx", "ix", "ox", "fx", "gh", "ih", "oh", "fh"};
-    auto entry = [&](const std::string& name, int store, int part, int k, int c, int r, bool bias) {
-        plan::Entry e;
-        e.name = name;
-        e.oihw[0] = k; e.oihw[1] = c; e.oihw[2] = r; e.oihw[3] = r;
-        e.has_bias = bias;
-        e.store = store;
-        e.part = part;
-        pl->entries.push_back(e);
-    };
-    for (const plan::Conv& cv : pl->prog[plan::STEP_FIRST].convs) {
+    for (const plan::Conv& cv : pl->prog[0].convs) {
         if (cv.name == "lstm_0") {
             for (int i = 0; i < 3; ++i)
-                entry(std::string("lstm_0.conv_") + gates0[i] + "_lstm", store_of("lstm_0"), i, cg, cg, 3, true);
+                pl->w.list(std::string("lstm_0.conv_") + gates0[i] + "_lstm", pl->w.store_of("lstm_0"), i, cg, cg, 3, true);
             for (int i = 0; i < 8; ++i)
-                entry(std::string("lstm.conv_") + gates[i] + "_lstm", store_of("lstm"), i, cg, cg, 3, true);
+                pl->w.list(std::string("lstm.conv_") + gates[i] + "_lstm", pl->w.store_of("lstm"), i, cg, cg, 3, true);
             continue;
         }
-        entry(cv.name, store_of(cv.name), -1, cv.d.K, cv.d.C, cv.d.R, cv.has_bias);
+        pl->w.list(cv.name, pl->w.store_of(cv.name), -1, cv.d.K, cv.d.C, cv.d.R, cv.has_bias);
     }
     if (!ok) {
         up_unipose_lstm_plan_destroy(pl);
@@ -1226,44 +1183,26 @@ extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up
 
 extern "C" void up_unipose_lstm_plan_destroy(up_unipose_lstm_plan* pl) {
     if (!pl) return;
-    for (plan::Store& st : pl->stores) {
-        plan::dev_free(st.w_fwd);
-        plan::dev_free(st.bias);
-        plan::dev_free(st.stage_w);
-        plan::dev_free(st.stage_b);
-    }
+    pl->w.release();
     delete pl;
 }
 
-extern "C" int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* pl) { return pl ? (int)pl->entries.size() : UP_ERR_INVALID; }
+extern "C" int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* pl) { return plan::num_convs(pl ? &pl->w : nullptr); }
 
 extern "C" const char* up_unipose_lstm_plan_conv_name(const up_unipose_lstm_plan* pl, int i) {
-    return (pl && i >= 0 && i < (int)pl->entries.size()) ? pl->entries[i].name.c_str() : "";
+    return plan::conv_name(pl ? &pl->w : nullptr, i);
 }
 
 extern "C" int up_unipose_lstm_plan_conv_shape(const up_unipose_lstm_plan* pl, int i, int32_t* oihw, int32_t* has_bias) {
-    UP_REQUIRE(pl && oihw && i >= 0 && i < (int)pl->entries.size(), UP_ERR_INVALID, "unipose_lstm_plan_conv_shape: bad argument");
-    const plan::Entry& e = pl->entries[i];
-    memcpy(oihw, e.oihw, sizeof(e.oihw));
-    if (has_bias) *has_bias = e.has_bias ? 1 : 0;
-    return UP_OK;
+    return plan::conv_shape(pl ? &pl->w : nullptr, i, oihw, has_bias, "unipose_lstm_plan_conv_shape");
 }
 
 extern "C" int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* pl, int i, const float* w_oihw, const float* bias, void* stream) {
-    UP_REQUIRE(pl && w_oihw && i >= 0 && i < (int)pl->entries.size(), UP_ERR_INVALID, "unipose_lstm_plan_set_conv: bad argument");
-    plan::Entry& en = pl->entries[i];
-    plan::Store& st = pl->stores[en.store];
-    UP_REQUIRE((bias != nullptr) == en.has_bias, UP_ERR_INVALID, "unipose_lstm_plan_set_conv: %s %s a bias (folded network)",
-               en.name.c_str(), en.has_bias ? "needs" : "has no");
-    if (en.part < 0) {
-        if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) return e;
-        if (bias)
-            if (int e = up_copy2d(bias, st.d.K, st.bias, st.d.K, 1, st.d.K, stream)) return e;
-        for (plan::Entry& other : pl->entries)
-            if (other.name == en.name) other.set = true;
-        return UP_OK;
-    }
+    if (int e = plan::set_conv_check(pl ? &pl->w : nullptr, i, w_oihw, bias, "unipose_lstm_plan_set_conv")) return e;
+    plan::Entry& en = pl->w.entries[i];
+    if (en.part < 0) return plan::set_conv_whole(pl->w, i, w_oihw, bias, stream);
     // a gate part: rows [gate * cg, (gate + 1) * cg) of the stacked OIHW image, input channels from xoff on
+    plan::Store& st = pl->w.stores[en.store];
     const int cg = pl->cfg.num_classes + 2, taps = st.d.R * st.d.S;
     const int gate = en.part % 4, xoff = st.parts == 8 && en.part >= 4 ? st.d.C / 2 : 0;
     if (!st.staged) {
@@ -1276,7 +1215,7 @@ extern "C" int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* pl, int i, co
         return e;
     if (int e = up_copy2d(bias, cg, st.stage_b + (size_t)en.part * cg, cg, 1, cg, stream)) return e;
     en.set = true;
-    for (const plan::Entry& other : pl->entries)
+    for (const plan::Entry& other : pl->w.entries)
         if (other.store == en.store && !other.set) return UP_OK;
     // every part is set: the stacked bias (LSTM_0: g | i | o; LSTM: bx + bh per gate) and the packed image
     int e = st.parts == 3 ? up_copy2d(st.stage_b, 3 * cg, st.bias, 3 * cg, 1, 3 * cg, stream)
@@ -1290,20 +1229,20 @@ extern "C" size_t up_unipose_lstm_plan_workspace(const up_unipose_lstm_plan* pl)
 extern "C" size_t up_unipose_lstm_plan_flip_workspace(const up_unipose_lstm_plan* pl) { return pl ? pl->flip_ws_bytes : 0; }
 
 extern "C" size_t up_unipose_lstm_plan_program_workspace(const up_unipose_lstm_plan* pl, int program) {
-    return pl && program >= 0 && program < plan::LSTM_FORMS ? pl->prog[program].ws_bytes : 0;
+    return pl ? plan::program_workspace(plan::LSTM_PROGRAMS, pl->prog, program) : 0;
 }
 
 extern "C" size_t up_unipose_lstm_plan_state_bytes(const up_unipose_lstm_plan* pl) {
     return pl ? 2 * pl->state_half * sizeof(float) : 0;
 }
 
-// `need`: up_unipose_lstm_plan_workspace() for step and clip (as ever), the program's own for the evaluation entries
-static int lstm_ready(const up_unipose_lstm_plan* pl, size_t need, const void* workspace, size_t ws_bytes, const char* what) {
-    for (const plan::Entry& e : pl->entries)
-        UP_REQUIRE(e.set, UP_ERR_INVALID, "%s: weights of %s were never set (up_unipose_lstm_plan_set_conv)", what, e.name.c_str());
-    UP_REQUIRE(ws_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, UP_ERR_WORKSPACE,
-               "%s: workspace of %zu bytes (256-byte aligned) needed, got %zu", what, need, ws_bytes);
-    return UP_OK;
+// The program of an entry's arguments, ready and run: a too-small workspace is UP_ERR_WORKSPACE from this plan.  whole: step and clip
+// ask for up_unipose_lstm_plan_workspace() (as ever), the evaluation entries for their program's own need.
+static int launch(up_unipose_lstm_plan* pl, plan::Input input, bool flip, plan::Ending end, plan::State from, bool whole, const plan::Io& io,
+                  void* workspace, size_t ws_bytes, void* stream, const char* what) {
+    const Plan& prog = pl->prog[plan::find(plan::LSTM_PROGRAMS, input, flip, end, from)];
+    return plan::launch(pl->w, "up_unipose_lstm_plan_set_conv", prog, whole ? pl->ws_bytes : prog.ws_bytes, UP_ERR_WORKSPACE, io, workspace,
+                        ws_bytes, stream, what);
 }
 
 extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nchw, const float* center_nchw, const float* prev_hide,
@@ -1313,7 +1252,6 @@ extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nch
                "unipose_lstm_step: null argument");
     UP_REQUIRE((prev_hide == nullptr) == (prev_cell == nullptr), UP_ERR_INVALID,
                "unipose_lstm_step: prev_hide and prev_cell are both given (a later frame) or both NULL (the first frame)");
-    if (int e = lstm_ready(pl, pl->ws_bytes, workspace, ws_bytes, "unipose_lstm_step")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.center = center_nchw;
@@ -1322,34 +1260,28 @@ extern "C" int up_unipose_lstm_step(up_unipose_lstm_plan* pl, const float* x_nch
     io.heat = heat_nchw;
     io.cell = cell_nchw;
     io.hide = hide_nchw;
-    return plan::run(pl->prog[prev_hide ? plan::STEP_NEXT : plan::STEP_FIRST], io, static_cast<unsigned char*>(workspace), stream,
-                     "unipose_lstm_step");
+    return launch(pl, plan::IN_NCHW, false, plan::END_HEAT, prev_hide ? plan::STATE_NCHW : plan::STATE_NONE, true, io, workspace, ws_bytes,
+                  stream, "unipose_lstm_step");
 }
 
 extern "C" int up_unipose_lstm_clip(up_unipose_lstm_plan* pl, const float* x, const float* center, float* heat, float* cell_last,
                                     float* hide_last, void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x && center && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip: null argument");
-    if (int e = lstm_ready(pl, pl->ws_bytes, workspace, ws_bytes, "unipose_lstm_clip")) return e;
     plan::Io io;
     io.x = x;
     io.center = center;
     io.heat = heat;
     io.cell = cell_last;
     io.hide = hide_last;
-    return plan::run(pl->prog[plan::CLIP], io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip");
+    return launch(pl, plan::IN_CLIP, false, plan::END_HEAT, plan::STATE_NONE, true, io, workspace, ws_bytes, stream, "unipose_lstm_clip");
 }
 
-// ---- the evaluation entries of the video plan (ABI 10 additions) ---------------------------------------------------------------
+// the evaluation entries
 extern "C" int up_unipose_lstm_clip_keypoints(up_unipose_lstm_plan* pl, const float* x, const float* center, int out_h, int out_w,
                                               int32_t* idx, float* preds_xy, float* maxvals, float* cell_last, float* hide_last,
                                               void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x && center && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_clip_keypoints: null argument");
-    const int h = (pl->cfg.height - 1) / 8 + 1, w = (pl->cfg.width - 1) / 8 + 1;
-    UP_REQUIRE((out_h == h && out_w == w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
-               "unipose_lstm_clip_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h,
-               out_w, h, w, pl->cfg.height, pl->cfg.width);
-    const Plan& prog = pl->prog[plan::CLIP_KEYPOINTS];
-    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_keypoints")) return e;
+    if (int e = plan::grid_ok(out_h, out_w, pl->cfg.height, pl->cfg.width, "unipose_lstm_clip_keypoints")) return e;
     plan::Io io;
     io.x = x;
     io.center = center;
@@ -1360,30 +1292,20 @@ extern "C" int up_unipose_lstm_clip_keypoints(up_unipose_lstm_plan* pl, const fl
     io.maxvals = maxvals;
     io.cell = cell_last;
     io.hide = hide_last;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_keypoints");
-}
-
-// the channel permutation of a flip-test call: refused here, before the first launch of the program (like perm_ok)
-static int lstm_perm_ok(const up_unipose_lstm_plan* pl, const int32_t* perm, const char* what) {
-    const int C = pl->cfg.num_classes + 1;
-    UP_REQUIRE(C <= 256, UP_ERR_UNSUPPORTED, "%s: %d heat-map channels (up_flip_merge takes up to 256)", what, C);
-    for (int j = 0; j < C; ++j)
-        UP_REQUIRE(perm[j] >= 0 && perm[j] < C, UP_ERR_INVALID, "%s: perm[%d] = %d outside 0..%d", what, j, (int)perm[j], C - 1);
-    return UP_OK;
+    return launch(pl, plan::IN_CLIP, false, plan::END_DECODE, plan::STATE_NONE, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_clip_keypoints");
 }
 
 extern "C" int up_unipose_lstm_clip_flip(up_unipose_lstm_plan* pl, const float* x, const float* center, const int32_t* perm_host,
                                          float* heat, void* workspace, size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && x && center && perm_host && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip_flip: null argument");
-    if (int e = lstm_perm_ok(pl, perm_host, "unipose_lstm_clip_flip")) return e;
-    const Plan& prog = pl->prog[plan::CLIP_FLIP];
-    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_flip")) return e;
+    if (int e = plan::perm_ok(pl->cfg.num_classes + 1, "heat-map", perm_host, "unipose_lstm_clip_flip")) return e;
     plan::Io io;
     io.x = x;
     io.center = center;
     io.perm = perm_host;
     io.heat = heat;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_flip");
+    return launch(pl, plan::IN_CLIP, true, plan::END_HEAT, plan::STATE_NONE, false, io, workspace, ws_bytes, stream, "unipose_lstm_clip_flip");
 }
 
 extern "C" int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* pl, const float* x, const float* center, const int32_t* perm_host,
@@ -1392,9 +1314,7 @@ extern "C" int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* pl, const 
     UP_REQUIRE(pl && x && center && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_clip_final_preds: null argument");
     UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_lstm_clip_final_preds: res %d, %d", res0, res1);
     if (perm_host)
-        if (int e = lstm_perm_ok(pl, perm_host, "unipose_lstm_clip_final_preds")) return e;
-    const Plan& prog = pl->prog[perm_host ? plan::CLIP_FLIP_PREDS : plan::CLIP_PREDS];
-    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_clip_final_preds")) return e;
+        if (int e = plan::perm_ok(pl->cfg.num_classes + 1, "heat-map", perm_host, "unipose_lstm_clip_final_preds")) return e;
     plan::Io io;
     io.x = x;
     io.center = center;
@@ -1405,7 +1325,8 @@ extern "C" int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* pl, const 
     io.preds = preds_xy;
     io.coords = coords_xy;
     io.maxvals = maxvals;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_clip_final_preds");
+    return launch(pl, plan::IN_CLIP, perm_host != nullptr, plan::END_FINAL, plan::STATE_NONE, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_clip_final_preds");
 }
 
 extern "C" int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* pl, const float* x_nchw, const float* center_nchw, void* state,
@@ -1415,12 +1336,7 @@ extern "C" int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* pl, const 
                "unipose_lstm_stream_keypoints: null argument");
     UP_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 255) == 0, UP_ERR_INVALID,
                "unipose_lstm_stream_keypoints: a 256-byte aligned state buffer of up_unipose_lstm_plan_state_bytes() bytes is needed");
-    const int h = (pl->cfg.height - 1) / 8 + 1, w = (pl->cfg.width - 1) / 8 + 1;
-    UP_REQUIRE((out_h == h && out_w == w) || (out_h == pl->cfg.height && out_w == pl->cfg.width), UP_ERR_INVALID,
-               "unipose_lstm_stream_keypoints: a %d x %d grid; the plan decodes on the heat-maps' %d x %d or the input's %d x %d", out_h,
-               out_w, h, w, pl->cfg.height, pl->cfg.width);
-    const Plan& prog = pl->prog[first ? plan::STREAM_FIRST : plan::STREAM_NEXT];
-    if (int e = lstm_ready(pl, prog.ws_bytes, workspace, ws_bytes, "unipose_lstm_stream_keypoints")) return e;
+    if (int e = plan::grid_ok(out_h, out_w, pl->cfg.height, pl->cfg.width, "unipose_lstm_stream_keypoints")) return e;
     plan::Io io;
     io.x = x_nchw;
     io.center = center_nchw;
@@ -1432,5 +1348,6 @@ extern "C" int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* pl, const 
     io.preds = preds_xy;
     io.maxvals = maxvals;
     io.heat = heat_nchw;
-    return plan::run(prog, io, static_cast<unsigned char*>(workspace), stream, "unipose_lstm_stream_keypoints");
+    return launch(pl, plan::IN_NCHW, false, plan::END_DECODE, first ? plan::STATE_NONE : plan::STATE_BUFFER, false, io, workspace, ws_bytes,
+                  stream, "unipose_lstm_stream_keypoints");
 }

@@ -72,7 +72,68 @@ def _check_out(who, name, t, shape, dev, dtype=torch.float32):
     return t
 
 
-class UniPosePlan:
+class _Plan:
+    """What the two plan classes share: device and stream, the aligned workspace, `out` tensors, the flip test's permutation and
+    the end of the plan.  `_prefix` names the C functions of the plan; `out_channels` are the channels of its heat-maps."""
+    _prefix = None
+    bbox = False
+
+    def _create(self, cfg, device):
+        L = _C.lib()
+        self.cfg, self.device, self.workspace = cfg, device, None
+        self._plan = C.c_void_p()
+        _C.check(getattr(L, self._prefix + "_create")(C.byref(cfg), C.byref(self._plan)), self._prefix[3:] + "_create")
+        self._ws(getattr(L, self._prefix + "_workspace")(self._plan))
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+
+    def _ws(self, need=None):
+        """the 256-byte aligned (pointer, bytes) of `self.workspace`, grown first where it is smaller than `need` bytes"""
+        if need is not None and (self.workspace is None or self.workspace.numel() < max(need, 256) + 256):
+            self.workspace = torch.empty(max(need, 256) + 256, dtype=torch.uint8, device=self.device)
+        ws = self.workspace
+        off = (-ws.data_ptr()) % 256
+        return ws.data_ptr() + off, ws.numel() - off
+
+    def _flip_ws(self):
+        """the flip test keeps the first pass's heat-maps while the network runs again: a larger workspace, made at the first call"""
+        return self._ws(getattr(_C.lib(), self._prefix + "_flip_workspace")(self._plan))
+
+    def _out(self, who, out, shape):
+        """the caller's `out` tensor if it is what the plan writes, or a new one"""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        return _check_out(who, "out", out, shape, self.device)
+
+    def _outs(self, who, out, names, shapes, dtypes=None, word="triple"):
+        """the caller's `out` tuple if every tensor in it is what the plan writes, or new tensors"""
+        dtypes = dtypes or (torch.float32,) * len(names)
+        if out is None:
+            return tuple(torch.empty(s, dtype=d, device=self.device) for s, d in zip(shapes, dtypes))
+        if len(out) != len(names):
+            raise ValueError(f"{who}: `out` is a ({', '.join(names)}) {word}")
+        return tuple(_check_out(who, n, t, s, self.device, d) for n, t, s, d in zip(names, out, shapes, dtypes))
+
+    def _perm(self, dataset, pairs):
+        from . import ops, protocol
+        return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, self.bbox, pairs), self.out_channels)
+
+    def close(self):
+        if self._plan:
+            getattr(_C.lib(), self._prefix + "_destroy")(self._plan)
+            self._plan = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class UniPosePlan(_Plan):
+    _prefix = "up_unipose_plan"
+
     def __init__(self, model, batch: int, height: int, width: int):
         if model.training:
             raise ValueError("UniPosePlan captures the inference forward: call model.eval() first")
@@ -82,26 +143,18 @@ class UniPosePlan:
         w0 = model.backbone.conv1.weight
         if not w0.is_cuda and not _C._ALLOW_HOST_POINTERS:
             raise _C.UniPoseHipError("UniPosePlan needs a CUDA(HIP) model; there is no CPU fallback")
-        self.device = w0.device
         self.bbox = bool(getattr(model, "bbox", False))
         self.num_classes = model.num_classes
         out_channels = model.decoder.last_conv[8].out_channels
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
-        self.cfg = _Config(batch, height, width, os_, out_channels)
-        self._plan = C.c_void_p()
-        L = _C.lib()
-        _C.check(L.up_unipose_plan_create(C.byref(self.cfg), C.byref(self._plan)), "unipose_plan_create")
+        self._create(_Config(batch, height, width, os_, out_channels), w0.device)
         self.batch, self.height, self.width, self.out_channels = batch, height, width, out_channels
         # heat-map size: three ceil-halvings (7x7 stride-2 stem, 3x3 stride-2 max-pool, layer2's stride 2), the arithmetic of
         # plan.hip's build(): ceil(H / 8), NOT H // 8 — the two differ whenever H % 8 != 0 (a 52 x 52 input gives 7 x 7 maps)
         self.map_height, self.map_width = (height - 1) // 8 + 1, (width - 1) // 8 + 1
         # what plan(x) writes: the maps themselves, or (stride != 8) the maps up-sampled to the input size
         self.out_height, self.out_width = (height, width) if self.upsampled else (self.map_height, self.map_width)
-        self.workspace = torch.empty(max(L.up_unipose_plan_workspace(self._plan), 256) + 256, dtype=torch.uint8, device=self.device)
         self.refresh(model)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
 
     def refresh(self, model):
         """(re)load the weights: BatchNorm folded in float64 and rounded once, like checkpoint.fold_batchnorm / load_folded"""
@@ -115,16 +168,10 @@ class UniPosePlan:
 
     def __call__(self, x: torch.Tensor, out: torch.Tensor = None):
         x = self._input(x)
-        shape = (self.batch, self.out_channels, self.out_height, self.out_width)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"UniPosePlan: `out` is {tuple(out.shape)} {out.dtype} on {out.device} (contiguous: {out.is_contiguous()}), "
-                             f"the plan writes a contiguous float32 {shape} on {self.device}")
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
+        out = self._out("UniPosePlan", out, (self.batch, self.out_channels, self.out_height, self.out_width))
+        ws, nbytes = self._ws()
         forward = _C.lib().up_unipose_forward_upsampled if self.upsampled else _C.lib().up_unipose_forward
-        _C.check(forward(self._plan, x.data_ptr(), out.data_ptr(), ws.data_ptr() + off, ws.numel() - off, self._stream()),
+        _C.check(forward(self._plan, x.data_ptr(), out.data_ptr(), ws, nbytes, self._stream()),
                  "unipose_forward_upsampled" if self.upsampled else "unipose_forward")
         if self.bbox:                   # model/unipose.py:34-35
             return out[:, 0:self.num_classes + 1], out[:, self.num_classes + 1:]
@@ -139,19 +186,12 @@ class UniPosePlan:
         if full_resolution is None:
             full_resolution = self.upsampled
         B, C_ = self.batch, self.out_channels
-        shapes = ((B, C_, 2), (B, C_, 1), (B, C_))
-        dtypes = (torch.float32, torch.float32, torch.int32)
-        if out is None:
-            out = tuple(torch.empty(s, dtype=d, device=self.device) for s, d in zip(shapes, dtypes))
-        elif len(out) != 3:
-            raise ValueError("UniPosePlan.keypoints: `out` is a (preds, maxvals, idx) triple")
-        preds, maxvals, idx = (_check_out("UniPosePlan.keypoints", n, t, s, self.device, d)
-                               for n, t, s, d in zip(("preds", "maxvals", "idx"), out, shapes, dtypes))
+        preds, maxvals, idx = self._outs("UniPosePlan.keypoints", out, ("preds", "maxvals", "idx"), ((B, C_, 2), (B, C_, 1), (B, C_)),
+                                         (torch.float32, torch.float32, torch.int32))
         oh, ow = (self.height, self.width) if full_resolution else (self.map_height, self.map_width)
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
+        ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_keypoints(self._plan, x.data_ptr(), oh, ow, idx.data_ptr(), preds.data_ptr(), maxvals.data_ptr(),
-                                               ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_keypoints")
+                                               ws, nbytes, self._stream()), "unipose_keypoints")
         return preds, maxvals, idx
 
     def persons(self, x: torch.Tensor, dataset: str, max_persons: int = 16, out=None):
@@ -171,31 +211,14 @@ class UniPosePlan:
             raise ValueError(f"max_persons {max_persons}: 1..{ops.PERSONS_CAP}")
         x = self._input(x)
         B = self.batch
-        shapes = ((B, max_persons, 19, 2), (B,), (B,))
         if out is None:
             out = ops._persons_out(B, max_persons, 19, self.device)[:3]
-        elif len(out) != 3:
-            raise ValueError("UniPosePlan.persons: `out` is a (kpts, count, status) triple")
-        kpts, count, status = (_check_out("UniPosePlan.persons", n, t, s, self.device, torch.int32)
-                               for n, t, s in zip(("kpts", "count", "status"), out, shapes))
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
+        kpts, count, status = self._outs("UniPosePlan.persons", out, ("kpts", "count", "status"), ((B, max_persons, 19, 2), (B,), (B,)),
+                                         (torch.int32,) * 3)
+        ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_persons(self._plan, x.data_ptr(), f, 1, 14, max_persons, count.data_ptr(), status.data_ptr(),
-                                             kpts.data_ptr(), ws.data_ptr() + off, ws.numel() - off, self._stream()), "unipose_persons")
+                                             kpts.data_ptr(), ws, nbytes, self._stream()), "unipose_persons")
         return kpts, count, status
-
-    def _perm(self, dataset, pairs):
-        from . import ops, protocol
-        return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, self.bbox, pairs), self.out_channels)
-
-    def _flip_ws(self):
-        """the flip test keeps the first pass's heat-maps while the trunk runs again: a larger workspace, made at the first call"""
-        need = max(_C.lib().up_unipose_plan_flip_workspace(self._plan), 256) + 256
-        if self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
 
     def flip_heatmaps(self, x: torch.Tensor, dataset: str = None, pairs=None, out: torch.Tensor = None):
         """The flip test in one call (``up_unipose_flip_forward``): the network on `x` and on the mirrored `x`, the second maps
@@ -204,11 +227,7 @@ class UniPosePlan:
         tensor on the maps' own grid ceil(H/8) x ceil(W/8), also for a model with ``stride != 8`` and with the box head."""
         x = self._input(x)
         perm = self._perm(dataset, pairs)
-        shape = (self.batch, self.out_channels, self.map_height, self.map_width)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        else:
-            _check_out("UniPosePlan.flip_heatmaps", "out", out, shape, self.device)
+        out = self._out("UniPosePlan.flip_heatmaps", out, (self.batch, self.out_channels, self.map_height, self.map_width))
         ws, nbytes = self._flip_ws()
         _C.check(_C.lib().up_unipose_flip_forward(self._plan, x.data_ptr(), perm, out.data_ptr(), ws, nbytes, self._stream()),
                  "unipose_flip_forward")
@@ -233,18 +252,9 @@ class UniPosePlan:
                 raise ValueError(f"UniPosePlan.final_preds: {inv.shape[0]} centres for a batch of {self.batch}")
             inv = inv.to(self.device)
         B, C_ = self.batch, self.out_channels
-        shapes = ((B, C_, 2), (B, C_, 2), (B, C_, 1))
-        if out is None:
-            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
-        elif len(out) != 3:
-            raise ValueError("UniPosePlan.final_preds: `out` is a (preds, coords, maxvals) triple")
-        preds, coords, maxvals = (_check_out("UniPosePlan.final_preds", n, t, s, self.device)
-                                  for n, t, s in zip(("preds", "coords", "maxvals"), out, shapes))
-        if flip:
-            ws, nbytes = self._flip_ws()
-        else:
-            off = (-self.workspace.data_ptr()) % 256
-            ws, nbytes = self.workspace.data_ptr() + off, self.workspace.numel() - off
+        preds, coords, maxvals = self._outs("UniPosePlan.final_preds", out, ("preds", "coords", "maxvals"),
+                                            ((B, C_, 2), (B, C_, 2), (B, C_, 1)))
+        ws, nbytes = self._flip_ws() if flip else self._ws()
         _C.check(_C.lib().up_unipose_final_preds(self._plan, x.data_ptr(), perm, None if inv is None else inv.data_ptr(), int(res[0]),
                                                  int(res[1]), preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
                                                  self._stream()), "unipose_final_preds")
@@ -253,12 +263,7 @@ class UniPosePlan:
     # ---- from source frames: the crop (up_crop_to_nhwc) in front of the same programs ----------------------------------------------
     def _frame_ws(self, program):
         """a program from frames keeps the mirrored input through the first trunk: its own need, made at the first call (`_flip_ws`)"""
-        need = max(_C.lib().up_unipose_plan_program_workspace(self._plan, _C.PROGRAM_FROM_FRAMES + program), 256) + 256
-        if self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
+        return self._ws(_C.lib().up_unipose_plan_program_workspace(self._plan, _C.PROGRAM_FROM_FRAMES + program))
 
     def _frame_args(self, who, frames, center, scale, frame_of, rot, valid_hw):
         """the arguments of up_crop_to_nhwc as the two entries take them, and the tensors that must outlive the call"""
@@ -299,11 +304,7 @@ class UniPosePlan:
         cropped input, with `flip` to ``flip_heatmaps`` of it (`dataset` / `pairs` as there)."""
         args, keep = self._frame_args("frame_heatmaps", frames, center, scale, frame_of, rot, valid_hw)
         perm = self._perm(dataset, pairs) if flip else None
-        shape = (self.batch, self.out_channels, self.map_height, self.map_width)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        else:
-            _check_out("UniPosePlan.frame_heatmaps", "out", out, shape, self.device)
+        out = self._out("UniPosePlan.frame_heatmaps", out, (self.batch, self.out_channels, self.map_height, self.map_width))
         ws, nbytes = self._frame_ws(4 if flip else 0)
         _C.check(_C.lib().up_unipose_frame_heatmaps(self._plan, *args, perm, out.data_ptr(), ws, nbytes, self._stream()),
                  "unipose_frame_heatmaps")
@@ -323,13 +324,8 @@ class UniPosePlan:
         res = [self.map_width, self.map_height] if res is None else protocol._res(res)
         inv = torch.from_numpy(protocol.inverse_maps(center, scale, res)).to(self.device)
         B, C_ = self.batch, self.out_channels
-        shapes = ((B, C_, 2), (B, C_, 2), (B, C_, 1))
-        if out is None:
-            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
-        elif len(out) != 3:
-            raise ValueError("UniPosePlan.frame_final_preds: `out` is a (preds, coords, maxvals) triple")
-        preds, coords, maxvals = (_check_out("UniPosePlan.frame_final_preds", n, t, s, self.device)
-                                  for n, t, s in zip(("preds", "coords", "maxvals"), out, shapes))
+        preds, coords, maxvals = self._outs("UniPosePlan.frame_final_preds", out, ("preds", "coords", "maxvals"),
+                                            ((B, C_, 2), (B, C_, 2), (B, C_, 1)))
         ws, nbytes = self._frame_ws(5 if flip else 6)
         _C.check(_C.lib().up_unipose_frame_final_preds(self._plan, *args, perm, inv.data_ptr(), int(res[0]), int(res[1]),
                                                        preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), ws, nbytes,
@@ -337,24 +333,13 @@ class UniPosePlan:
         del keep
         return preds, coords, maxvals
 
-    def close(self):
-        if self._plan:
-            _C.lib().up_unipose_plan_destroy(self._plan)
-            self._plan = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:       # noqa: BLE001  (interpreter shutdown)
-            pass
-
 
 class _LstmConfig(C.Structure):
     """up_unipose_lstm_config"""
     _fields_ = [(n, C.c_int32) for n in ("batch", "frames", "height", "width", "output_stride", "num_classes")]
 
 
-class UniPoseLSTMPlan:
+class UniPoseLSTMPlan(_Plan):
     """The video model's inference forward through the C ABI (``up_unipose_lstm_step`` / ``up_unipose_lstm_clip``, ABI 10 additions).
 
     Built from an eval-mode ``unipose_lstm`` (BatchNorm folded like ``checkpoint.fold_batchnorm``).  Two forms, equal bits to the
@@ -373,6 +358,7 @@ class UniPoseLSTMPlan:
     first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
     module ignores them at iter == 0).  Weights are captured at construction: ``refresh(model)`` after changing them.  Inference only.
     """
+    _prefix = "up_unipose_lstm_plan"
 
     def __init__(self, model, batch: int, height: int, width: int, frames: int = 1):
         if model.training:
@@ -384,21 +370,12 @@ class UniPoseLSTMPlan:
         w0 = model.backbone.conv1.weight
         if not w0.is_cuda and not _C._ALLOW_HOST_POINTERS:
             raise _C.UniPoseHipError("UniPoseLSTMPlan needs a CUDA(HIP) model; there is no CPU fallback")
-        self.device = w0.device
         self.num_classes = K = model.num_classes
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
-        self.cfg = _LstmConfig(batch, frames, height, width, os_, K)
-        self._plan = C.c_void_p()
-        L = _C.lib()
-        _C.check(L.up_unipose_lstm_plan_create(C.byref(self.cfg), C.byref(self._plan)), "unipose_lstm_plan_create")
+        self._create(_LstmConfig(batch, frames, height, width, os_, K), w0.device)
         self.batch, self.frames, self.height, self.width = batch, frames, height, width
-        self.out_height, self.out_width = (height - 1) // 8 + 1, (width - 1) // 8 + 1
-        self.workspace = torch.empty(max(L.up_unipose_lstm_plan_workspace(self._plan), 256) + 256, dtype=torch.uint8,
-                                     device=self.device)
+        self.out_channels, self.out_height, self.out_width = K + 1, (height - 1) // 8 + 1, (width - 1) // 8 + 1
         self.refresh(model)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
 
     def refresh(self, model):
         """(re)load the weights: BatchNorm folded in float64 and rounded once; the gate weights are stacked by the plan"""
@@ -416,19 +393,6 @@ class UniPoseLSTMPlan:
             t = t.unsqueeze(0).expand(self.batch, -1, -1, -1)
         return self._input(t, (self.batch,) + c, what)
 
-    def _outs(self, out, shapes):
-        names = ("heat", "cell", "hide")
-        if out is None:
-            return tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
-        if len(out) != 3:
-            raise ValueError("UniPoseLSTMPlan: `out` is a (heat, cell, hide) triple")
-        return tuple(_check_out("UniPoseLSTMPlan", n, t, s, self.device) for n, t, s in zip(names, out, shapes))
-
-    def _ws(self):
-        ws = self.workspace
-        off = (-ws.data_ptr()) % 256
-        return ws.data_ptr() + off, ws.numel() - off
-
     def step(self, frame: torch.Tensor, centermap: torch.Tensor, prev=None, first: bool = None, out=None):
         """One frame: frame (B, 3, H, W), centermap (B, 1, H, W), prev = None or (hide, cell) -> heat (B, K+1, h, w), cell, hide
         (B, K+2, h, w).  first (default: prev is None) selects LSTM_0, which reads no state."""
@@ -442,7 +406,7 @@ class UniPoseLSTMPlan:
         ph = pc = None
         if not first:
             ph, pc = self._state(prev[0], "previous hide"), self._state(prev[1], "previous cell")
-        heat, cell, hide = self._outs(out, [(B, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
+        heat, cell, hide = self._outs("UniPoseLSTMPlan", out, ("heat", "cell", "hide"), [(B, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
         ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_lstm_step(self._plan, x.data_ptr(), cm.data_ptr(), None if first else ph.data_ptr(),
                                                None if first else pc.data_ptr(), heat.data_ptr(), cell.data_ptr(), hide.data_ptr(),
@@ -455,7 +419,8 @@ class UniPoseLSTMPlan:
         B, T, H, W, h, w, K = self.batch, self.frames, self.height, self.width, self.out_height, self.out_width, self.num_classes
         x = self._input(frames, (B, T, 3, H, W), "clip")
         cm = self._input(centermaps, (B, T, 1, H, W), "centre maps")
-        heat, cell, hide = self._outs(out, [(B, T, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
+        heat, cell, hide = self._outs("UniPoseLSTMPlan", out, ("heat", "cell", "hide"),
+                                      [(B, T, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
         ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_lstm_clip(self._plan, x.data_ptr(), cm.data_ptr(), heat.data_ptr(), cell.data_ptr(),
                                                hide.data_ptr(), ws, nbytes, self._stream()), "unipose_lstm_clip")
@@ -466,24 +431,6 @@ class UniPoseLSTMPlan:
         B, T, H, W = self.batch, self.frames, self.height, self.width
         return self._input(frames, (B, T, 3, H, W), "clip"), self._input(centermaps, (B, T, 1, H, W), "centre maps")
 
-    def _tuple_out(self, who, out, names, shapes, dtypes):
-        if out is None:
-            return tuple(torch.empty(s, dtype=d, device=self.device) for s, d in zip(shapes, dtypes))
-        if len(out) != len(names):
-            raise ValueError(f"UniPoseLSTMPlan.{who}: `out` is a ({', '.join(names)}) tuple")
-        return tuple(_check_out("UniPoseLSTMPlan." + who, n, t, s, self.device, d) for n, t, s, d in zip(names, out, shapes, dtypes))
-
-    def _perm(self, dataset, pairs):
-        from . import ops, protocol
-        return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, False, pairs), self.num_classes + 1)
-
-    def _flip_ws(self):
-        """the flip test keeps the first pass's heat-maps while the clip runs again: a larger workspace, made at the first call"""
-        need = max(_C.lib().up_unipose_lstm_plan_flip_workspace(self._plan), 256) + 256
-        if self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws()
-
     def clip_keypoints(self, frames: torch.Tensor, centermaps: torch.Tensor, full_resolution: bool = False, out=None):
         """The joints of the whole clip without its NCHW heat-maps (``up_unipose_lstm_clip_keypoints``): (preds (B, T, K+1, 2),
         maxvals (B, T, K+1, 1), idx (B, T, K+1) int32, cell, hide (B, K+2, h, w) of the last frame) — equal bits to
@@ -492,9 +439,10 @@ class UniPoseLSTMPlan:
         B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
         x, cm = self._clip_inputs(frames, centermaps)
         f32 = torch.float32
-        preds, maxvals, idx, cell, hide = self._tuple_out(
-            "clip_keypoints", out, ("preds", "maxvals", "idx", "cell", "hide"),
-            ((B, T, K + 1, 2), (B, T, K + 1, 1), (B, T, K + 1), (B, K + 2, h, w), (B, K + 2, h, w)), (f32, f32, torch.int32, f32, f32))
+        preds, maxvals, idx, cell, hide = self._outs(
+            "UniPoseLSTMPlan.clip_keypoints", out, ("preds", "maxvals", "idx", "cell", "hide"),
+            ((B, T, K + 1, 2), (B, T, K + 1, 1), (B, T, K + 1), (B, K + 2, h, w), (B, K + 2, h, w)), (f32, f32, torch.int32, f32, f32),
+            word="tuple")
         oh, ow = (self.height, self.width) if full_resolution else (h, w)
         ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_lstm_clip_keypoints(self._plan, x.data_ptr(), cm.data_ptr(), oh, ow, idx.data_ptr(),
@@ -512,11 +460,7 @@ class UniPoseLSTMPlan:
         B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
         x, cm = self._clip_inputs(frames, centermaps)
         perm = self._perm(dataset, pairs)
-        shape = (B, T, K + 1, h, w)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        else:
-            _check_out("UniPoseLSTMPlan.clip_flip_heatmaps", "out", out, shape, self.device)
+        out = self._out("UniPoseLSTMPlan.clip_flip_heatmaps", out, (B, T, K + 1, h, w))
         ws, nbytes = self._flip_ws()
         _C.check(_C.lib().up_unipose_lstm_clip_flip(self._plan, x.data_ptr(), cm.data_ptr(), perm, out.data_ptr(), ws, nbytes,
                                                     self._stream()), "unipose_lstm_clip_flip")
@@ -546,8 +490,7 @@ class UniPoseLSTMPlan:
                                  f"{None if sc is None else tuple(sc.shape)}, one crop per frame is {(B, T, 2)} / {(B, T)}")
             inv = torch.from_numpy(protocol.inverse_maps(c.reshape(B * T, 2), sc.reshape(B * T), res)).to(self.device)
         shapes = ((B, T, K + 1, 2), (B, T, K + 1, 2), (B, T, K + 1, 1))
-        preds, coords, maxvals = self._tuple_out("clip_final_preds", out, ("preds", "coords", "maxvals"), shapes,
-                                                 (torch.float32,) * 3)
+        preds, coords, maxvals = self._outs("UniPoseLSTMPlan.clip_final_preds", out, ("preds", "coords", "maxvals"), shapes, word="tuple")
         ws, nbytes = self._flip_ws() if flip else self._ws()
         _C.check(_C.lib().up_unipose_lstm_clip_final_preds(self._plan, x.data_ptr(), cm.data_ptr(), perm,
                                                            None if inv is None else inv.data_ptr(), int(res[0]), int(res[1]),
@@ -578,9 +521,8 @@ class UniPoseLSTMPlan:
                              f"on {self.device})")
         if heat is not None:
             _check_out("UniPoseLSTMPlan.stream", "heat", heat, (B, K + 1, h, w), self.device)
-        idx = torch.empty((B, K + 1), dtype=torch.int32, device=self.device)
-        preds = torch.empty((B, K + 1, 2), dtype=torch.float32, device=self.device)
-        maxvals = torch.empty((B, K + 1, 1), dtype=torch.float32, device=self.device)
+        preds, maxvals, idx = self._outs("UniPoseLSTMPlan.stream", None, ("preds", "maxvals", "idx"),
+                                         ((B, K + 1, 2), (B, K + 1, 1), (B, K + 1)), (torch.float32, torch.float32, torch.int32))
         oh, ow = (H, W) if full_resolution else (h, w)
         ws, nbytes = self._ws()
         _C.check(_C.lib().up_unipose_lstm_stream_keypoints(self._plan, x.data_ptr(), cm.data_ptr(), state.data_ptr(), int(bool(first)),
@@ -588,14 +530,3 @@ class UniPoseLSTMPlan:
                                                            None if heat is None else heat.data_ptr(), ws, nbytes, self._stream()),
                  "unipose_lstm_stream_keypoints")
         return preds, maxvals, idx
-
-    def close(self):
-        if self._plan:
-            _C.lib().up_unipose_lstm_plan_destroy(self._plan)
-            self._plan = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:       # noqa: BLE001  (interpreter shutdown)
-            pass
