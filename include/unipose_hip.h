@@ -642,6 +642,40 @@ int up_augment_image(const void* src_hwc, int src_type, int B, int Hs, int Ws, i
 int up_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of, const int32_t* valid_hw,
                     const double* inv, int B, float border, float mean, float stdv, float* y_nhwc, float* y_flip_nhwc, int Ho, int Wo,
                     int ldy, void* stream);
+/* The clip form (ABI 10 addition; the video plan from source frames below): B x T samples, sample (b, t) with frame_of (B,T) (or
+ * NULL: F must equal B * T and sample (b, t) reads frame b * T + t), valid_hw (F,2) per source frame and inv (B,T,6) on the
+ * caller's side batch-major; the outputs y_nhwc and y_flip_nhwc (T * B, Ho, Wo, ldy) FRAME-major, as the video plan keeps a clip.
+ * Contract: image t * B + b of y_nhwc has equal bits to sample b * T + t of up_crop_to_nhwc called with B * T samples and the same
+ * (flattened) arguments, y_flip_nhwc to its y_flip_nhwc; T = 1 is up_crop_to_nhwc itself.  The same kernel with the reordering
+ * folded in (one device function holds the resample): one thread per output pixel, 16-byte stores, pad channels zero, an index of
+ * frame_of outside 0 .. F-1 makes the sample all border and loads nothing, at most 2^21 threads per grid, 64-bit indexing.
+ * UP_ERR_INVALID (nothing launched): T <= 0, frame_of == NULL with F != B * T, and what up_crop_to_nhwc refuses. */
+int up_clip_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                         const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv, float* y_nhwc,
+                         float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream);
+
+/* ---- the pooled centre map straight from the centre (ABI 10 additions) ----
+ * What the video network does with a centre map is AvgPool2d(9,8,1) down to the heat-maps' grid (uniposeLSTM.py:75,114): these
+ * write the pooled map from the centre coordinates, the (N,1,H,W) maps never exist.
+ * center_xy (N,2) resp. (B,T,2) float64 on the device, (column, row) in pixels of the H x W map; sigma as up_make_gaussian_maps.
+ * Output: channel coff of y (N, P, Q, ldy) resp. frame-major (T * B, P, Q, ldy) from the batch-major centres; no other channel of y is
+ * touched.  P = (H - 7) / 8 + 1, Q = (W - 7) / 8 + 1.
+ * Contract: equal bits to up_avgpool9s8_fwd / up_clip_avgpool9s8_fwd / up_clip_avgpool9s8_flip_fwd of
+ * up_make_gaussian_maps(center_xy, N, H, W, sigma).  Every tap is up_make_gaussian_maps' value (float64 exp(-d2 / 2 / sigma / sigma),
+ * clipped to <= 1, < 0.0099 -> 0, rounded to float32) and the window, the divisor and the order of the sum are the pooling's: rows
+ * ascending, within a row ascending columns of the plane that is pooled, one float32 add per tap, one float32 division at the end.
+ * _flip: the plane is the mirrored map m[r][w] = g[r][W-1-w]; its tap at column w is the Gaussian about (cx, cy) evaluated at column
+ * W-1-w — NOT a Gaussian about W-1-cx, whose subtraction rounds differently.
+ * A tap with d2 > 9.4 sigma^2 is taken as the 0 it is without evaluating exp (the cut lies at d2 = 2 sigma^2 ln(1 / 0.0099) =
+ * 9.2304 sigma^2).  A NaN centre propagates NaN, an infinite one gives 0, as in the two-call form.
+ * One thread per pooled pixel, consecutive threads consecutive q; no LDS, no atomics.
+ * UP_ERR_INVALID (nothing launched): a null pointer, a size <= 0, sigma <= 0 (or NaN), coff outside 0 .. ldy-1, P, Q not the pooled
+ * size or <= 0, H * W beyond the int32 range. */
+int up_center_pool(const double* center_xy, double sigma, float* y, int ldy, int coff, int N, int H, int W, int P, int Q, void* stream);
+int up_clip_center_pool(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                        void* stream);
+int up_clip_center_pool_flip(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                             void* stream);
 
 /* ---- PCK / PCKh evaluation (utils/evaluate.py:5-29 calc_dists / dist_acc, :58-172 accuracy) ----
  * From the joint coordinates of the predicted and the target heat-maps (two up_heatmap_argmax calls), entirely on
@@ -836,7 +870,31 @@ int up_unipose_frame_final_preds(up_unipose_plan* plan, const void* src_hwc, int
  * 2 clip, 3 clip_keypoints, 4 clip_flip, 5 clip_final_preds with and 6 without the flip test, 7 stream-first, 8 stream-next, 0 for any
  * other k.  up_unipose_lstm_plan_workspace() is the largest of 0..3 and 6..8 (step and clip ask for exactly that, as before),
  * up_unipose_lstm_plan_flip_workspace() of 4 and 5; an evaluation entry asks for its own program's need.  Unset weights, a too-small
- * workspace, a perm entry outside 0..K, res <= 0 and a null required pointer are refused before anything is launched. */
+ * workspace, a perm entry outside 0..K, res <= 0 and a null required pointer are refused before anything is launched.
+ *
+ * From source frames (ABI 10 additions): three entries put the crop and up_center_pool in front of these programs, in place of their
+ * layout pass and of the pooling of full-resolution centre maps.  src_hwc .. stdv are up_clip_crop_to_nhwc's arguments with
+ * B = batch, T = frames (C = 3, Ho x Wo = H x W, ldy = 4; crop_inv (B,T,6) its inv), for the stream up_crop_to_nhwc's with
+ * crop_inv (B,6); center_xy (B,T,2) resp. (B,2) float64 on the device and sigma are up_clip_center_pool's resp. up_center_pool's:
+ * the centre in pixels of the H x W network input.  In the flip test ONE crop launch fills the input and the mirrored input, and
+ * the mirrored pass pools its centre map from the same coordinates with up_clip_center_pool_flip.  Every convolution launch is one
+ * the corresponding program above makes, so the results equal, bit for bit, those of the entry above called with the crop
+ * (up_augment_image) and up_make_gaussian_maps(center_xy) as x and centre maps.
+ *   up_unipose_lstm_clip_frame_heatmaps       perm_host == NULL: up_unipose_lstm_clip, cell_last / hide_last optional as there;
+ *                                             perm_host != NULL: up_unipose_lstm_clip_flip, and a non-NULL cell_last or hide_last is
+ *                                             refused (there are two states).
+ *   up_unipose_lstm_clip_frame_final_preds    up_unipose_lstm_clip_final_preds; inv (B,T,2,3) or NULL, res0, res1: the way back as
+ *                                             there, independent of crop_inv.
+ *   up_unipose_lstm_stream_frame_final_preds  one camera frame in, joints in frame pixels out: up_crop_to_nhwc with B samples,
+ *                                             up_center_pool, the step program with the state in `state` exactly as
+ *                                             up_unipose_lstm_stream_keypoints keeps it (`first` as there), then up_final_preds straight
+ *                                             from the NHWC output of conv5: preds_xy, coords_xy (may be NULL) (B,K+1,2), maxvals (B,K+1);
+ *                                             inv (B,2,3) or NULL; heat_nchw (B,K+1,h,w) may be NULL.  No flip test inside a stream.
+ * Refused before anything is launched: what the crop and the centre-pool kernels refuse, and what the entries above refuse (a NULL
+ * or misaligned state included); the outputs are then untouched.  Workspace: each asks for
+ * up_unipose_lstm_plan_program_workspace(plan, UP_PROGRAM_FROM_FRAMES + k), k = 2, 4, 5, 6, 7, 8 naming the program it otherwise
+ * equals (0 for any other k; the flip forms keep the mirrored input alive through the first pass); neither
+ * up_unipose_lstm_plan_workspace() nor up_unipose_lstm_plan_flip_workspace() changes. */
 typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
 typedef struct {
     int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */
@@ -869,6 +927,21 @@ int up_unipose_lstm_clip_final_preds(up_unipose_lstm_plan* plan, const float* x,
 int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* plan, const float* x_nchw, const float* center_nchw, void* state, int first,
                                      int out_h, int out_w, int32_t* idx, float* preds_xy, float* maxvals, float* heat_nchw,
                                      void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_lstm_clip_frame_heatmaps(up_unipose_lstm_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                        const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                        float mean, float stdv, const double* center_xy, double sigma, const int32_t* perm_host,
+                                        float* heat, float* cell_last, float* hide_last, void* workspace, size_t workspace_bytes,
+                                        void* stream);
+int up_unipose_lstm_clip_frame_final_preds(up_unipose_lstm_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                           const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                           float mean, float stdv, const double* center_xy, double sigma, const int32_t* perm_host,
+                                           const double* inv, int res0, int res1, float* preds_xy, float* coords_xy, float* maxvals,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+int up_unipose_lstm_stream_frame_final_preds(up_unipose_lstm_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                             const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                             float mean, float stdv, const double* center_xy, double sigma, void* state, int first,
+                                             const double* inv, int res0, int res1, float* preds_xy, float* coords_xy, float* maxvals,
+                                             float* heat_nchw, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg; no reference counterpart) ----
  * Between begin/end every MFMA convolution launch is bracketed by two hipEvents on its stream;

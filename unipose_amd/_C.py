@@ -197,6 +197,16 @@ SIGNATURES = {
     "up_unipose_lstm_clip_flip": (_i, [_p, _p, _p, C.POINTER(C.c_int32), _p, _p, _sz, _p]),
     "up_unipose_lstm_clip_final_preds": (_i, [_p, _p, _p, C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_unipose_lstm_stream_keypoints": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "up_clip_crop_to_nhwc": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _f, _f, _f, _p, _p, _i, _i, _i, _p]),
+    "up_center_pool": (_i, [_p, C.c_double, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_center_pool": (_i, [_p, C.c_double, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_center_pool_flip": (_i, [_p, C.c_double, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_unipose_lstm_clip_frame_heatmaps": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, _p, C.c_double, C.POINTER(C.c_int32), _p,
+                                                 _p, _p, _p, _sz, _p]),
+    "up_unipose_lstm_clip_frame_final_preds": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, _p, C.c_double, C.POINTER(C.c_int32),
+                                                    _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "up_unipose_lstm_stream_frame_final_preds": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, _p, C.c_double, _p, _i, _p, _i, _i,
+                                                      _p, _p, _p, _p, _p, _sz, _p]),
     "up_profile_variants": (_i, []),
     "up_profile_variant_name": (C.c_char_p, [_i]),
     "up_profile_begin": (_i, []),
@@ -205,7 +215,9 @@ SIGNATURES = {
     "up_profile_end": (_i, [C.POINTER(C.c_double), _i]),
 }
 
-PROGRAM_FROM_FRAMES = 256          # UP_PROGRAM_FROM_FRAMES: up_unipose_plan_program_workspace(plan, 256 + k), k = 0, 4, 5, 6
+# UP_PROGRAM_FROM_FRAMES: up_unipose_plan_program_workspace(plan, 256 + k), k = 0, 4, 5, 6;
+# up_unipose_lstm_plan_program_workspace(plan, 256 + k), k = 2, 4, 5, 6, 7, 8
+PROGRAM_FROM_FRAMES = 256
 
 _lib = None
 # Set ONLY by tests/conftest.py when it points the binding at the CPU emulation build of the same

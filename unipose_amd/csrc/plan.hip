@@ -75,7 +75,7 @@ struct Conv {
 enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW, DECODE, PERSONS, TO_NHWC_FLIP, MERGE, FINAL, CROP,
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL, CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL,
-    STATE_IN, STATE_OUT
+    STATE_IN, STATE_OUT, CLIP_CROP, CENTER_POOL, CLIP_CENTER_POOL, CLIP_CENTER_POOL_FLIP
 };
 enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
 // Sizes, strides and physical channel counts come from the tensors an op names; the fields below are what they do not hold.
@@ -327,7 +327,9 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
 }
 
 // ---- what a program is made of ---------------------------------------------------------------------------------------------------
-enum Input { IN_NCHW, IN_FRAMES, IN_CLIP };    // the caller's NCHW batch; source frames through up_crop_to_nhwc; a (B, T, ...) clip
+// the caller's NCHW batch; source frames through up_crop_to_nhwc; a (B, T, ...) clip; a clip of source frames through
+// up_clip_crop_to_nhwc
+enum Input { IN_NCHW, IN_FRAMES, IN_CLIP, IN_CLIP_FRAMES };
 enum Ending {
     END_HEAT,          // NCHW heat-maps on their own grid
     END_UPSAMPLED,     // ... bilinearly up-sampled to the input size first, as the module does at stride != 8 (model/unipose.py:31-32)
@@ -369,6 +371,10 @@ static const Program IMAGE_PROGRAMS[] = {
 // state; the clip programs its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True), the flip test running the
 // whole clip twice, each pass with its own recurrent state, so a flip program returns none.  The stream programs are the step
 // programs with the state in the caller's buffer and up_heatmap_decode at the end; their NCHW heat-maps are optional.
+// From frames (the rows numbered UP_PROGRAM_FROM_FRAMES + k, k the program the row otherwise equals): ONE crop launch stands in place
+// of the layout pass(es) and, in the flip rows, fills the mirrored input too, which then stays alive through the first pass; the
+// pooled centre map comes straight from the centre coordinates (up_center_pool and its clip forms), in the mirrored pass from the
+// same coordinates through the _flip kernel.  The stream rows end in up_final_preds.  Every convolution launch is row k's.
 static const Program LSTM_PROGRAMS[] = {
     {0, IN_NCHW, false, END_HEAT, COUNTS_PLAIN, STATE_NONE, STATE_NCHW},        // up_unipose_lstm_step, the first frame ...
     {1, IN_NCHW, false, END_HEAT, COUNTS_PLAIN, STATE_NCHW, STATE_NCHW},        // ... and a later one
@@ -379,6 +385,12 @@ static const Program LSTM_PROGRAMS[] = {
     {6, IN_CLIP, false, END_FINAL, COUNTS_PLAIN},       // ... and without the flip test
     {7, IN_NCHW, false, END_DECODE, COUNTS_PLAIN, STATE_NONE, STATE_BUFFER},    // up_unipose_lstm_stream_keypoints, first ...
     {8, IN_NCHW, false, END_DECODE, COUNTS_PLAIN, STATE_BUFFER, STATE_BUFFER},  // ... and not
+    {UP_PROGRAM_FROM_FRAMES + 2, IN_CLIP_FRAMES, false, END_HEAT, COUNTS_OWN, STATE_NONE, STATE_NCHW},   // up_unipose_lstm_clip_frame_heatmaps
+    {UP_PROGRAM_FROM_FRAMES + 4, IN_CLIP_FRAMES, true, END_HEAT, COUNTS_OWN},
+    {UP_PROGRAM_FROM_FRAMES + 5, IN_CLIP_FRAMES, true, END_FINAL, COUNTS_OWN},  // up_unipose_lstm_clip_frame_final_preds
+    {UP_PROGRAM_FROM_FRAMES + 6, IN_CLIP_FRAMES, false, END_FINAL, COUNTS_OWN},
+    {UP_PROGRAM_FROM_FRAMES + 7, IN_FRAMES, false, END_FINAL, COUNTS_OWN, STATE_NONE, STATE_BUFFER},     // up_unipose_lstm_stream_frame_final_preds
+    {UP_PROGRAM_FROM_FRAMES + 8, IN_FRAMES, false, END_FINAL, COUNTS_OWN, STATE_BUFFER, STATE_BUFFER},
 };
 template <size_t N>
 static int find(const Program (&table)[N], Input input, bool flip, Ending end, State from = STATE_NONE) {
@@ -449,17 +461,23 @@ struct LstmPass {
 // One pass of a video program up to conv5: the trunk once on the T * B frame-major images (T = 1 unless the input is a clip), the
 // recurrence frame by frame on rows of frame-major state tensors, the head once on the T * B hidden states.  Stacked gate
 // convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).  mirrored: the pass of the flip test.
-static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored) {
-    const bool clip = g.input == IN_CLIP;
+// mirror: from frames, the mirrored input the first pass's crop launch fills for the second.
+static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored, Ref& mirror) {
+    const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
+    const bool frames = g.input == IN_FRAMES || g.input == IN_CLIP_FRAMES;
     const int B = c.batch, T = clip ? c.frames : 1, n = T * B;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
     int h = c.height, w = c.width;
-    Ref x;
-    x.id = p.tensor(n, h, w, 4);
-    {
+    Ref x = mirror;
+    if (!(frames && mirrored)) {
+        x.id = p.tensor(n, h, w, 4);
         Op op;
-        op.kind = !clip ? TO_NHWC : mirrored ? CLIP_TO_NHWC_FLIP : CLIP_TO_NHWC;
+        op.kind = frames ? (clip ? CLIP_CROP : CROP) : !clip ? TO_NHWC : mirrored ? CLIP_TO_NHWC_FLIP : CLIP_TO_NHWC;
         op.out = x;
+        if (frames && g.flip) {
+            mirror.id = p.tensor(n, h, w, 4);
+            op.aux = mirror;
+        }
         op.ext = X;
         op.n = B; op.frames = T; op.ch = 3;
         p.push(op);
@@ -476,7 +494,8 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
     const int ldz = p.tensors[z.id].c;       // == ldo either way
     {
         Op op;
-        op.kind = !clip ? POOL : mirrored ? CLIP_POOL_FLIP : CLIP_POOL;
+        if (frames) op.kind = !clip ? CENTER_POOL : mirrored ? CLIP_CENTER_POOL_FLIP : CLIP_CENTER_POOL;
+        else op.kind = !clip ? POOL : mirrored ? CLIP_POOL_FLIP : CLIP_POOL;
         op.out = z;
         op.ext = CENTER;
         op.n = B; op.frames = T;
@@ -552,13 +571,14 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
 }
 
 static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g) {
-    const bool clip = g.input == IN_CLIP;
+    const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
     const int B = c.batch, T = clip ? c.frames : 1;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
-    const LstmPass a = lstm_pass(p, c, g, false);
+    Ref mirror;
+    const LstmPass a = lstm_pass(p, c, g, false, mirror);
     Op op;
     if (g.flip) {
-        const LstmPass m = lstm_pass(p, c, g, true);
+        const LstmPass m = lstm_pass(p, c, g, true, mirror);
         op.kind = MERGE;                       // in place (NHWC): out == a with equal strides; both passes are frame-major
         op.in = a.y; op.aux = m.y; op.out = a.y;
         op.n = T * B; op.ch = hc;
@@ -583,7 +603,7 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& 
         op.in = cl; op.half = 1;
         p.push(op);
         op = Op();
-        op.kind = DECODE;
+        op.kind = g.end == END_FINAL ? FINAL : DECODE;
         op.in = a.y;
         op.n = B; op.ch = hc;
         p.push(op);
@@ -637,6 +657,8 @@ struct Io {
     const int32_t* valid_hw = nullptr;
     const double* crop_inv = nullptr;
     float border = 0.f, mean = 0.f, stdv = 0.f;
+    const double* center_xy = nullptr;      // the centre-pool kinds: the arguments of up_center_pool
+    double sigma = 0.0;
     const float* in(Ext e) const { return e == X ? x : e == CENTER ? center : e == PREV_HIDE ? prev_hide : prev_cell; }
     float* out(Ext e) const { return e == HEAT ? heat : e == CELL ? cell : hide; }
 };
@@ -743,6 +765,20 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
         case CLIP_FINAL:
             e = up_clip_final_preds(ptr(op.in), image, 1, i.c, op.n, op.frames, op.ch, i.h, i.w, io.res0, io.res1, io.inv, io.preds,
                                     io.coords, io.maxvals, stream);
+            break;
+        case CLIP_CROP:
+            e = up_clip_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.ch, io.frame_of, io.valid_hw, io.crop_inv, op.n,
+                                     op.frames, io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), o.h, o.w, o.c, stream);
+            break;
+        case CENTER_POOL:
+            e = up_center_pool(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.src_h, op.src_w, o.h, o.w, stream);
+            break;
+        case CLIP_CENTER_POOL:
+            e = up_clip_center_pool(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
+            break;
+        case CLIP_CENTER_POOL_FLIP:
+            e = up_clip_center_pool_flip(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
+                                         stream);
             break;
         case STATE_IN:                         // whole padded rows: the pad channels stay the zeros the plan wrote
             e = up_copy2d(io.state + op.half * io.state_half, o.c, ptr(op.out), o.c, (int64_t)o.n * o.h * o.w, o.c, stream);
@@ -1059,15 +1095,15 @@ extern "C" int up_unipose_final_preds(up_unipose_plan* pl, const float* x_nchw, 
 }
 
 // From source frames: the crop of up_crop_to_nhwc in front of the same programs.  Its own refusals (source type, sizes,
-// frame_of == NULL with F != batch, std) come from its wrapper, which is the program's first launch: nothing runs before it.
-static int frame_io(const up_unipose_plan* pl, plan::Io& io, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+// frame_of == NULL with F != samples, std) come from its wrapper, which is the program's first launch: nothing runs before it.
+// samples: the image plan's batch, the video plan's B * T (a clip) or B (a stream).
+static int frame_io(int samples, plan::Io& io, const void* src_hwc, int src_type, int F, int Hs, int Ws,
                     const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border, float mean, float stdv,
                     const char* what) {
     UP_REQUIRE(src_hwc && crop_inv, UP_ERR_INVALID, "%s: null source frames or crop maps", what);
     UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "%s: source type %d", what, src_type);
     UP_REQUIRE(F > 0 && Hs > 0 && Ws > 0, UP_ERR_INVALID, "%s: %d frames of %d x %d", what, F, Hs, Ws);
-    UP_REQUIRE(frame_of || F == pl->cfg.batch, UP_ERR_INVALID, "%s: no frame_of with %d frames for a batch of %d", what, F,
-               pl->cfg.batch);
+    UP_REQUIRE(frame_of || F == samples, UP_ERR_INVALID, "%s: no frame_of with %d frames for a batch of %d", what, F, samples);
     UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "%s: std %g", what, (double)stdv);
     io.src = src_hwc;
     io.src_type = src_type;
@@ -1089,7 +1125,8 @@ extern "C" int up_unipose_frame_heatmaps(up_unipose_plan* pl, const void* src_hw
                                          size_t ws_bytes, void* stream) {
     UP_REQUIRE(pl && heat_nchw && workspace, UP_ERR_INVALID, "unipose_frame_heatmaps: null argument");
     plan::Io io;
-    if (int e = frame_io(pl, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, "unipose_frame_heatmaps"))
+    if (int e = frame_io(pl->cfg.batch, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv,
+                         "unipose_frame_heatmaps"))
         return e;
     if (perm_host)
         if (int e = plan::perm_ok(pl->cfg.out_channels, "output", perm_host, "unipose_frame_heatmaps")) return e;
@@ -1106,7 +1143,7 @@ extern "C" int up_unipose_frame_final_preds(up_unipose_plan* pl, const void* src
     UP_REQUIRE(pl && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_frame_final_preds: null argument");
     UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_frame_final_preds: res %d, %d", res0, res1);
     plan::Io io;
-    if (int e = frame_io(pl, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv,
+    if (int e = frame_io(pl->cfg.batch, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv,
                          "unipose_frame_final_preds"))
         return e;
     if (perm_host)
@@ -1350,4 +1387,90 @@ extern "C" int up_unipose_lstm_stream_keypoints(up_unipose_lstm_plan* pl, const 
     io.heat = heat_nchw;
     return launch(pl, plan::IN_NCHW, false, plan::END_DECODE, first ? plan::STATE_NONE : plan::STATE_BUFFER, false, io, workspace, ws_bytes,
                   stream, "unipose_lstm_stream_keypoints");
+}
+
+// From source frames: up_clip_crop_to_nhwc (a stream: up_crop_to_nhwc) and the centre pool in front of the same programs.  What the
+// centre-pool kernels refuse of the caller's arguments (the sizes are the plan's) is refused here, before the crop is launched.
+static int lstm_frame_io(int samples, plan::Io& io, const void* src_hwc, int src_type, int F, int Hs, int Ws, const int32_t* frame_of,
+                         const int32_t* valid_hw, const double* crop_inv, float border, float mean, float stdv, const double* center_xy,
+                         double sigma, const char* what) {
+    if (int e = frame_io(samples, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, what)) return e;
+    UP_REQUIRE(center_xy, UP_ERR_INVALID, "%s: null centre coordinates", what);
+    UP_REQUIRE(sigma > 0, UP_ERR_INVALID, "%s: sigma %g", what, sigma);
+    io.center_xy = center_xy;
+    io.sigma = sigma;
+    return UP_OK;
+}
+
+extern "C" int up_unipose_lstm_clip_frame_heatmaps(up_unipose_lstm_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                                   const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                                   float mean, float stdv, const double* center_xy, double sigma,
+                                                   const int32_t* perm_host, float* heat, float* cell_last, float* hide_last,
+                                                   void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && heat && workspace, UP_ERR_INVALID, "unipose_lstm_clip_frame_heatmaps: null argument");
+    UP_REQUIRE(!perm_host || (!cell_last && !hide_last), UP_ERR_INVALID,
+               "unipose_lstm_clip_frame_heatmaps: the flip test returns no state (there are two): cell_last and hide_last must be NULL");
+    plan::Io io;
+    if (int e = lstm_frame_io(pl->cfg.batch * pl->cfg.frames, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean,
+                              stdv, center_xy, sigma, "unipose_lstm_clip_frame_heatmaps"))
+        return e;
+    if (perm_host)
+        if (int e = plan::perm_ok(pl->cfg.num_classes + 1, "heat-map", perm_host, "unipose_lstm_clip_frame_heatmaps")) return e;
+    io.perm = perm_host;
+    io.heat = heat;
+    io.cell = cell_last;
+    io.hide = hide_last;
+    return launch(pl, plan::IN_CLIP_FRAMES, perm_host != nullptr, plan::END_HEAT, plan::STATE_NONE, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_clip_frame_heatmaps");
+}
+
+extern "C" int up_unipose_lstm_clip_frame_final_preds(up_unipose_lstm_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                                      const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv,
+                                                      float border, float mean, float stdv, const double* center_xy, double sigma,
+                                                      const int32_t* perm_host, const double* inv, int res0, int res1, float* preds_xy,
+                                                      float* coords_xy, float* maxvals, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_clip_frame_final_preds: null argument");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_lstm_clip_frame_final_preds: res %d, %d", res0, res1);
+    plan::Io io;
+    if (int e = lstm_frame_io(pl->cfg.batch * pl->cfg.frames, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean,
+                              stdv, center_xy, sigma, "unipose_lstm_clip_frame_final_preds"))
+        return e;
+    if (perm_host)
+        if (int e = plan::perm_ok(pl->cfg.num_classes + 1, "heat-map", perm_host, "unipose_lstm_clip_frame_final_preds")) return e;
+    io.perm = perm_host;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    return launch(pl, plan::IN_CLIP_FRAMES, perm_host != nullptr, plan::END_FINAL, plan::STATE_NONE, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_clip_frame_final_preds");
+}
+
+extern "C" int up_unipose_lstm_stream_frame_final_preds(up_unipose_lstm_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                                        const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv,
+                                                        float border, float mean, float stdv, const double* center_xy, double sigma,
+                                                        void* state, int first, const double* inv, int res0, int res1, float* preds_xy,
+                                                        float* coords_xy, float* maxvals, float* heat_nchw, void* workspace,
+                                                        size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_stream_frame_final_preds: null argument");
+    UP_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 255) == 0, UP_ERR_INVALID,
+               "unipose_lstm_stream_frame_final_preds: a 256-byte aligned state buffer of up_unipose_lstm_plan_state_bytes() bytes is needed");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_lstm_stream_frame_final_preds: res %d, %d", res0, res1);
+    plan::Io io;
+    if (int e = lstm_frame_io(pl->cfg.batch, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, center_xy,
+                              sigma, "unipose_lstm_stream_frame_final_preds"))
+        return e;
+    io.state = static_cast<float*>(state);
+    io.state_half = pl->state_half;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    io.heat = heat_nchw;
+    return launch(pl, plan::IN_FRAMES, false, plan::END_FINAL, first ? plan::STATE_NONE : plan::STATE_BUFFER, false, io, workspace, ws_bytes,
+                  stream, "unipose_lstm_stream_frame_final_preds");
 }

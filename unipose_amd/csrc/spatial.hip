@@ -372,8 +372,10 @@ __global__ void __launch_bounds__(256) gap_bwd_kernel(const T* dy, T* dx, int ld
 // output pixel (p, q) of the H x W plane `x`: the arithmetic of both launches below (a clip's centre maps pool to the same bits)
 // FLIP: ... of the MIRRORED plane, m[h][w] = x[h][W - 1 - w], read in place: the window and the divisor are those of column q of
 // m (the padding sits on one side, so this is not the window of column Q - 1 - q of x), and the sum runs over ascending w of m
-template <bool FLIP = false>
-__device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int p, int q) {
+// tap(h, c): the value at row h, column c of the plane that is stored (c = W - 1 - w under FLIP).  The ONE statement of the
+// window, the divisor and the order of the sum: the pooling launches and the centre-pool launches both return this.
+template <bool FLIP, typename Tap>
+__device__ __forceinline__ float avgpool9s8_window(int H, int W, int p, int q, Tap tap) {
     int hs = p * 8 - 1, ws = q * 8 - 1;
     int he = min(hs + 9, H + 1), we = min(ws + 9, W + 1);
     float div = (float)((he - hs) * (we - ws));
@@ -383,8 +385,12 @@ __device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int
     we = min(we, W);
     float s = 0.f;
     for (int h = hs; h < he; ++h)
-        for (int w = ws; w < we; ++w) s += x[h * W + (FLIP ? W - 1 - w : w)];
+        for (int w = ws; w < we; ++w) s += tap(h, FLIP ? W - 1 - w : w);
     return s / div;
+}
+template <bool FLIP = false>
+__device__ __forceinline__ float avgpool9s8_at(const float* x, int H, int W, int p, int q) {
+    return avgpool9s8_window<FLIP>(H, W, p, q, [=](int h, int c) { return x[h * W + c]; });
 }
 __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int H, int W,
                                                          int P, int Q, int64_t total) {
@@ -819,6 +825,34 @@ __global__ void __launch_bounds__(256) gaussian_map_kernel(const double* center,
     const int n = (int)(t / H);
     out[e] = target_gauss((double)x, (double)y, center[2 * n], center[2 * n + 1], sigma);
 }
+// The pooled centre map straight from the centre (up_center_pool and its clip forms, include/unipose_hip.h): avgpool9s8_window over
+// target_gauss, so the (N, 1, H, W) maps never exist.  One thread per pooled pixel, consecutive threads consecutive q; only channel
+// coff of a pixel is written.  CLIP: frame-major rows from batch-major centres.  FLIP: the plane is the mirrored map, whose column w
+// holds target_gauss at column W - 1 - w of the map about (cx, cy) — not a Gaussian about W - 1 - cx, whose subtraction rounds
+// differently.
+// skip: a tap with d2 > 9.4 * sigma^2 is not evaluated.  target_gauss returns 0 where exp(-d2 / 2 / sigma / sigma) < 0.0099, that is
+// where d2 / (2 sigma^2) > ln(1 / 0.0099) = 4.6152; the bound asks for 4.7, a margin of 1.8 %, against the few 1e-16 relative error
+// of the products and divisions on both sides and exp's last-place error (exp(-4.7) = 0.00910).  d2 is target_gauss's own
+// statement, so it is the value target_gauss would test; a skipped tap adds the +0.0f target_gauss would have returned.  A NaN
+// centre gives a NaN d2, which fails the comparison and is evaluated: NaN propagates.  An infinite centre gives d2 = inf: skipped
+// as the 0 that exp(-inf) is (at a sigma so large that the bound is inf too, it is evaluated).
+template <bool CLIP, bool FLIP>
+__global__ void __launch_bounds__(256) center_pool_kernel(const double* center, double sigma, double skip, float* y, int ldy, int coff,
+                                                          int B, int T, int H, int W, int P, int Q, int64_t total) {
+    UP_GRID_STRIDE(i, total) {
+        const int q = (int)(i % Q);
+        const int64_t t = i / Q;
+        const int p = (int)(t % P);
+        const int64_t f = t / P;
+        const int64_t n = CLIP ? clip_image(f, B, T) : f;
+        const double cx = center[2 * n], cy = center[2 * n + 1];
+        y[i * ldy + coff] = avgpool9s8_window<FLIP>(H, W, p, q, [=](int h, int c) {
+            const double dx = (double)c - cx, dy = (double)h - cy;
+            const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+            return d2 > skip ? 0.f : target_gauss((double)c, (double)h, cx, cy, sigma);
+        });
+    }
+}
 // Box-head targets (getBoundingBox, lsp_lspet_data.py:71-113 / bbc_data.py:23-72), every statement in float64 like Python's
 // floats; int() is trunc().  The reference calls the SECOND coordinate x and the first y, bounds x by `width` and y by `height`,
 // and then centres the Gaussian's column on the y-derived cell and its row on the x-derived one: kept as it is.
@@ -945,16 +979,18 @@ __global__ void __launch_bounds__(256) augment_image_kernel(const T* src, int Hs
 // (several persons of one frame share it); an index outside 0 .. F-1 is device data and makes the sample all border, nothing loaded.
 // One thread per output pixel, consecutive threads consecutive u: with ld = 4 a wave stores 1 KiB of consecutive pixels per
 // instruction, forwards into y and backwards into y_flip; the quads beyond the first are the zero pad channels.
-template <typename T>
+// CLIP (up_clip_crop_to_nhwc): the outputs are frame-major, image t * cB + b holds sample b * cT + t of the batch-major frame_of
+// and inv; everything else is the same code.
+template <typename T, bool CLIP>
 __global__ void __launch_bounds__(256) crop_to_nhwc_kernel(const T* src, int F, int Hs, int Ws, int C, const int32_t* frame_of,
                                                            const int32_t* valid_hw, const double* inv, float border, float mean,
                                                            float stdv, float* y, float* yf, int Ho, int Wo, int ld,
-                                                           long long total /* B*Ho*Wo */) {
+                                                           long long total /* B*Ho*Wo */, int cB, int cT) {
     UP_GRID_STRIDE(e, total) {
         const int u = (int)(e % Wo);
         const int64_t t = e / Wo;
         const int v = (int)(t % Ho);
-        const int64_t b = t / Ho;
+        const int64_t b = CLIP ? clip_image(t / Ho, cB, cT) : t / Ho;     // the sample; e stays the output pixel
         int64_t f = frame_of ? (int64_t)frame_of[b] : b;
         int Hv = 0, Wv = 0;
         if (f >= 0 && f < F) {
@@ -1675,31 +1711,96 @@ extern "C" int up_augment_image(const void* src_hwc, int src_type, int B, int Hs
                            total);
     return check_launch("augment_image");
 }
+// up_crop_to_nhwc (T == 0: B samples) and up_clip_crop_to_nhwc (B x T samples, frame-major outputs): one set of refusals, one kernel
+template <typename PIX, bool CLIP>
+static void crop_launch(const void* src_hwc, int F, int Hs, int Ws, int C, const int32_t* frame_of, const int32_t* valid_hw,
+                        const double* inv, int B, int T, float border, float mean, float stdv, float* y, float* yf, int Ho, int Wo, int ldy,
+                        long long total, void* stream) {
+    hipLaunchKernelGGL((crop_to_nhwc_kernel<PIX, CLIP>), dim3(grid_cap(total)), dim3(256), 0, as_stream(stream), (const PIX*)src_hwc, F,
+                       Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y, yf, Ho, Wo, ldy, total, B, T);
+}
+static int crop_to_nhwc(const char* what, const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                        const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv, float* y_nhwc,
+                        float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream) {
+    const bool clip = T != 0;
+    UP_REQUIRE(src_hwc && inv, UP_ERR_INVALID, "%s: null argument", what);
+    UP_REQUIRE(y_nhwc || y_flip_nhwc, UP_ERR_INVALID, "%s: both outputs are null", what);
+    UP_REQUIRE(y_nhwc != y_flip_nhwc, UP_ERR_INVALID, "%s: y_nhwc == y_flip_nhwc", what);
+    UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "%s: source type %d", what, src_type);
+    UP_REQUIRE(F > 0 && B > 0 && T >= 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, UP_ERR_INVALID,
+               "%s: %d samples (%d frames each) from %d frames of %d x %d to %d x %d", what, B, clip ? T : 1, F, Hs, Ws, Ho, Wo);
+    UP_REQUIRE(C >= 1 && C <= 4, UP_ERR_INVALID, "%s: %d channels (1 .. 4)", what, C);
+    UP_REQUIRE(ldy >= C && ldy % 4 == 0, UP_ERR_INVALID, "%s: ldy %d for %d channels (a multiple of 4)", what, ldy, C);
+    UP_REQUIRE((uintptr_t)y_nhwc % 16 == 0 && (uintptr_t)y_flip_nhwc % 16 == 0, UP_ERR_INVALID,
+               "%s: an output that is not 16-byte aligned", what);
+    const long long samples = (long long)B * (clip ? T : 1);
+    UP_REQUIRE(frame_of || F == samples, UP_ERR_INVALID, "%s: no frame_of with %d frames for %lld samples", what, F, samples);
+    UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "%s: std %g", what, (double)stdv);
+    const long long total = samples * Ho * Wo;
+    if (src_type == UP_PIX_U8) {
+        if (clip)
+            crop_launch<uint8_t, true>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
+                                       ldy, total, stream);
+        else
+            crop_launch<uint8_t, false>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho,
+                                        Wo, ldy, total, stream);
+    } else {
+        if (clip)
+            crop_launch<float, true>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
+                                     ldy, total, stream);
+        else
+            crop_launch<float, false>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
+                                      ldy, total, stream);
+    }
+    return check_launch(what);
+}
 extern "C" int up_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
                                const int32_t* valid_hw, const double* inv, int B, float border, float mean, float stdv, float* y_nhwc,
                                float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream) {
-    UP_REQUIRE(src_hwc && inv, UP_ERR_INVALID, "crop_to_nhwc: null argument");
-    UP_REQUIRE(y_nhwc || y_flip_nhwc, UP_ERR_INVALID, "crop_to_nhwc: both outputs are null");
-    UP_REQUIRE(y_nhwc != y_flip_nhwc, UP_ERR_INVALID, "crop_to_nhwc: y_nhwc == y_flip_nhwc");
-    UP_REQUIRE(src_type == UP_PIX_U8 || src_type == UP_PIX_F32, UP_ERR_INVALID, "crop_to_nhwc: source type %d", src_type);
-    UP_REQUIRE(F > 0 && B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, UP_ERR_INVALID,
-               "crop_to_nhwc: %d samples from %d frames of %d x %d to %d x %d", B, F, Hs, Ws, Ho, Wo);
-    UP_REQUIRE(C >= 1 && C <= 4, UP_ERR_INVALID, "crop_to_nhwc: %d channels (1 .. 4)", C);
-    UP_REQUIRE(ldy >= C && ldy % 4 == 0, UP_ERR_INVALID, "crop_to_nhwc: ldy %d for %d channels (a multiple of 4)", ldy, C);
-    UP_REQUIRE((uintptr_t)y_nhwc % 16 == 0 && (uintptr_t)y_flip_nhwc % 16 == 0, UP_ERR_INVALID,
-               "crop_to_nhwc: an output that is not 16-byte aligned");
-    UP_REQUIRE(frame_of || F == B, UP_ERR_INVALID, "crop_to_nhwc: no frame_of with %d frames for %d samples", F, B);
-    UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "crop_to_nhwc: std %g", (double)stdv);
-    const long long total = (long long)B * Ho * Wo;
-    if (src_type == UP_PIX_U8)
-        hipLaunchKernelGGL(crop_to_nhwc_kernel<uint8_t>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
-                           (const uint8_t*)src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho,
-                           Wo, ldy, total);
+    return crop_to_nhwc("crop_to_nhwc", src_hwc, src_type, F, Hs, Ws, C, frame_of, valid_hw, inv, B, 0, border, mean, stdv, y_nhwc,
+                        y_flip_nhwc, Ho, Wo, ldy, stream);
+}
+extern "C" int up_clip_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                    const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv,
+                                    float* y_nhwc, float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream) {
+    UP_REQUIRE(T > 0, UP_ERR_INVALID, "clip_crop_to_nhwc: %d frames per sample", T);
+    return crop_to_nhwc("clip_crop_to_nhwc", src_hwc, src_type, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc,
+                        y_flip_nhwc, Ho, Wo, ldy, stream);
+}
+
+// the three centre-pool entries: one set of refusals, one kernel
+static int center_pool(const char* what, bool clip, bool flip, const double* center_xy, double sigma, float* y, int ldy, int coff, int B,
+                       int T, int H, int W, int P, int Q, void* stream) {
+    UP_REQUIRE(center_xy && y, UP_ERR_INVALID, "%s: null argument", what);
+    UP_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && ldy > 0, UP_ERR_INVALID, "%s: %d x %d maps of %d x %d, ldy %d", what, B, T, H, W, ldy);
+    UP_REQUIRE(sigma > 0, UP_ERR_INVALID, "%s: sigma %g", what, sigma);
+    UP_REQUIRE(coff >= 0 && coff < ldy, UP_ERR_INVALID, "%s: channel %d of %d", what, coff, ldy);
+    UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1 && P > 0 && Q > 0, UP_ERR_INVALID, "%s: P,Q mismatch", what);
+    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "%s: %d x %d: a pixel index beyond the int32 range", what, H, W);
+    const int64_t total = (int64_t)T * B * P * Q;
+    const double skip = 9.4 * sigma * sigma;
+    if (!clip)
+        UP_LAUNCH_1D((center_pool_kernel<false, false>), total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P, Q,
+                     total);
+    else if (!flip)
+        UP_LAUNCH_1D((center_pool_kernel<true, false>), total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P, Q,
+                     total);
     else
-        hipLaunchKernelGGL(crop_to_nhwc_kernel<float>, dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
-                           (const float*)src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho,
-                           Wo, ldy, total);
-    return check_launch("crop_to_nhwc");
+        UP_LAUNCH_1D((center_pool_kernel<true, true>), total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P, Q,
+                     total);
+    return check_launch(what);
+}
+extern "C" int up_center_pool(const double* center_xy, double sigma, float* y, int ldy, int coff, int N, int H, int W, int P, int Q,
+                              void* stream) {
+    return center_pool("center_pool", false, false, center_xy, sigma, y, ldy, coff, N, 1, H, W, P, Q, stream);
+}
+extern "C" int up_clip_center_pool(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P,
+                                   int Q, void* stream) {
+    return center_pool("clip_center_pool", true, false, center_xy, sigma, y, ldy, coff, B, T, H, W, P, Q, stream);
+}
+extern "C" int up_clip_center_pool_flip(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W,
+                                        int P, int Q, void* stream) {
+    return center_pool("clip_center_pool_flip", true, true, center_xy, sigma, y, ldy, coff, B, T, H, W, P, Q, stream);
 }
 
 extern "C" int up_peak_mask(const float* maps, int nmaps, int H, int W, uint8_t* mask, void* stream) {

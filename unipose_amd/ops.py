@@ -2017,6 +2017,62 @@ def augment_image(pixels: torch.Tensor, inv, out_hw, border: float = 128.0, mean
     return out
 
 
+def _crop_to_nhwc(who, frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, border, mean, std):
+    """``crop_to_nhwc`` (clip = None) and ``clip_crop_to_nhwc`` (clip = (B, T)): the same checks, one call each"""
+    _dev_ok(frames)
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"{who}: uint8 or float32 frames, got {frames.dtype}")
+    if frames.dim() != 4:
+        raise ValueError(f"{who}: frames (F,H,W,C), got {tuple(frames.shape)}")
+    x = frames if frames.is_contiguous() else frames.contiguous()
+    nf, h, w, c = x.shape
+    m = torch.as_tensor(inv, dtype=torch.float64) if not (isinstance(inv, torch.Tensor) and inv.is_cuda) else None
+    if m is not None and not bool(torch.isfinite(m).all()):
+        raise ValueError(f"{who}: a map with a non-finite entry")
+    m = _as_f64(inv if m is None else m, x.device)
+    if clip is None:
+        if m.dim() == 3 and tuple(m.shape[1:]) == (2, 3):
+            m = m.reshape(-1, 6)
+        if m.dim() != 2 or m.shape[1] != 6 or m.shape[0] < 1:
+            raise ValueError(f"{who}: maps {tuple(m.shape)} ((B, 6) or (B, 2, 3) expected)")
+        b = m.shape[0]
+        lead, images = (b,), b
+    else:
+        nb, nt = int(clip[0]), int(clip[1])
+        if nb < 1 or nt < 1 or tuple(m.shape) not in ((nb, nt, 6), (nb, nt, 2, 3)):
+            raise ValueError(f"{who}: maps {tuple(m.shape)} for a clip of {nb} x {nt} ((B, T, 6) or (B, T, 2, 3) expected)")
+        m = m.reshape(nb * nt, 6)
+        b = nb * nt
+        lead, images = (nb, nt), b
+    fo = None
+    if frame_of is not None:
+        on_device = isinstance(frame_of, torch.Tensor) and frame_of.is_cuda
+        fo = torch.as_tensor(frame_of)
+        if tuple(fo.shape) != lead:
+            raise ValueError(f"{who}: frame_of {tuple(fo.shape)} for {b if clip is None else lead} maps")
+        if not on_device and not bool(((fo >= 0) & (fo < nf)).all()):
+            raise ValueError(f"{who}: a frame index outside 0 .. {nf - 1}")
+        fo = fo.to(device=x.device, dtype=torch.int32).contiguous()
+    elif nf != b:
+        raise ValueError(f"{who}: {b} maps for {nf} frames and no frame_of")
+    valid = None
+    if valid_hw is not None:
+        valid = torch.as_tensor(valid_hw).to(device=x.device, dtype=torch.int32).contiguous()
+        if tuple(valid.shape) != (nf, 2):
+            raise ValueError(f"{who}: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    shape = (images, max(ho, 0), max(wo, 0), max(int(ld), 0))
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    yf = torch.empty(shape, dtype=torch.float32, device=x.device) if flip else None
+    head = (x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, h, w, c, _ptr(fo), _ptr(valid), m.data_ptr())
+    tail = (float(border), float(mean), float(std), y.data_ptr(), _ptr(yf), ho, wo, int(ld), _stream(x))
+    if clip is None:
+        _C.check(_C.lib().up_crop_to_nhwc(*head, b, *tail), who)
+    else:
+        _C.check(_C.lib().up_clip_crop_to_nhwc(*head, lead[0], lead[1], *tail), who)
+    return (y, yf) if flip else y
+
+
 def crop_to_nhwc(frames: torch.Tensor, inv, out_hw, frame_of=None, valid_hw=None, flip: bool = False, ld: int = 4,
                  border: float = 128.0, mean: float = 128.0, std: float = 256.0):
     """The crop in front of the network in one launch (``up_crop_to_nhwc``, include/unipose_hip.h): frames (F,Hs,Ws,C) uint8 or
@@ -2028,46 +2084,53 @@ def crop_to_nhwc(frames: torch.Tensor, inv, out_hw, frame_of=None, valid_hw=None
     (y, y_flip), y_flip the horizontally mirrored y, written by the same launch.  Maps and frame indices are handled as in
     ``augment_image``: given on the host they are checked here (non-finite entries and indices outside 0 .. F-1 are refused);
     device tensors pass unchecked, and the kernel makes such a sample all border and reads nothing for it."""
-    _dev_ok(frames)
-    if frames.dtype not in (torch.uint8, torch.float32):
-        raise TypeError(f"crop_to_nhwc: uint8 or float32 frames, got {frames.dtype}")
-    if frames.dim() != 4:
-        raise ValueError(f"crop_to_nhwc: frames (F,H,W,C), got {tuple(frames.shape)}")
-    x = frames if frames.is_contiguous() else frames.contiguous()
-    nf, h, w, c = x.shape
-    m = torch.as_tensor(inv, dtype=torch.float64) if not (isinstance(inv, torch.Tensor) and inv.is_cuda) else None
-    if m is not None and not bool(torch.isfinite(m).all()):
-        raise ValueError("crop_to_nhwc: a map with a non-finite entry")
-    m = _as_f64(inv if m is None else m, x.device)
-    if m.dim() == 3 and tuple(m.shape[1:]) == (2, 3):
-        m = m.reshape(-1, 6)
-    if m.dim() != 2 or m.shape[1] != 6 or m.shape[0] < 1:
-        raise ValueError(f"crop_to_nhwc: maps {tuple(m.shape)} ((B, 6) or (B, 2, 3) expected)")
-    b = m.shape[0]
-    fo = None
-    if frame_of is not None:
-        on_device = isinstance(frame_of, torch.Tensor) and frame_of.is_cuda
-        fo = torch.as_tensor(frame_of)
-        if tuple(fo.shape) != (b,):
-            raise ValueError(f"crop_to_nhwc: frame_of {tuple(fo.shape)} for {b} maps")
-        if not on_device and not bool(((fo >= 0) & (fo < nf)).all()):
-            raise ValueError(f"crop_to_nhwc: a frame index outside 0 .. {nf - 1}")
-        fo = fo.to(device=x.device, dtype=torch.int32).contiguous()
-    elif nf != b:
-        raise ValueError(f"crop_to_nhwc: {b} maps for {nf} frames and no frame_of")
-    valid = None
-    if valid_hw is not None:
-        valid = torch.as_tensor(valid_hw).to(device=x.device, dtype=torch.int32).contiguous()
-        if tuple(valid.shape) != (nf, 2):
-            raise ValueError(f"crop_to_nhwc: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
-    ho, wo = int(out_hw[0]), int(out_hw[1])
-    shape = (b, max(ho, 0), max(wo, 0), max(int(ld), 0))
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
-    yf = torch.empty(shape, dtype=torch.float32, device=x.device) if flip else None
-    _C.check(_C.lib().up_crop_to_nhwc(x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, h, w, c, _ptr(fo), _ptr(valid), m.data_ptr(),
-                                      b, float(border), float(mean), float(std), y.data_ptr(), _ptr(yf), ho, wo, int(ld), _stream(x)),
-             "crop_to_nhwc")
-    return (y, yf) if flip else y
+    return _crop_to_nhwc("crop_to_nhwc", frames, inv, out_hw, None, frame_of, valid_hw, flip, ld, border, mean, std)
+
+
+def clip_crop_to_nhwc(frames: torch.Tensor, inv, out_hw, clip, frame_of=None, valid_hw=None, flip: bool = False, ld: int = 4,
+                      border: float = 128.0, mean: float = 128.0, std: float = 256.0):
+    """``crop_to_nhwc`` for a clip (``up_clip_crop_to_nhwc``): clip = (B, T), inv (B, T, 6) or (B, T, 2, 3) and frame_of (B, T)
+    batch-major (None: sample (b, t) reads frame b * T + t), valid_hw (F, 2) per frame.  Returns y (T * B, Ho, Wo, ld) FRAME-major,
+    image t * B + b the crop of sample (b, t) — equal bits to ``crop_to_nhwc`` of the flattened arguments, reordered — or with
+    `flip` the pair (y, y_flip)."""
+    return _crop_to_nhwc("clip_crop_to_nhwc", frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, border, mean, std)
+
+
+def center_pool(center_xy, hw, sigma: float = 3.0, out: torch.Tensor = None, coff: int = None, clip=None, flip: bool = False,
+                device=None):
+    """The pooled centre map straight from the centre (``up_center_pool`` / ``up_clip_center_pool`` / ``up_clip_center_pool_flip``):
+    center_xy (N, 2), or (B, T, 2) with clip = (B, T), in pixels of the hw = (H, W) map -> channel `coff` of `out`
+    (N or T * B, P, Q, ld) float32 NHWC (frame-major for a clip), P = (H - 7) // 8 + 1, Q = (W - 7) // 8 + 1; no other channel is
+    touched.  Without `out`: a new zero-filled (N, P, Q, 4) tensor, written at channel `coff` (default 0).  Equal bits to
+    AvgPool2d(9, 8, 1) of ``make_centermaps(center_xy, H, W, sigma)``; flip (clips only): of the mirrored maps."""
+    c = _as_f64(center_xy, device if out is None else out.device)
+    h, w = int(hw[0]), int(hw[1])
+    p, q = (h - 7) // 8 + 1, (w - 7) // 8 + 1
+    if clip is None:
+        if flip:
+            raise ValueError("center_pool: the mirrored form is a clip's (clip=(B, T))")
+        if c.dim() != 2 or c.shape[1] != 2 or c.shape[0] < 1:
+            raise ValueError(f"center_pool: centres {tuple(c.shape)} ((N, 2) expected)")
+        lead = (c.shape[0],)
+    else:
+        lead = (int(clip[0]), int(clip[1]))
+        if tuple(c.shape) != lead + (2,):
+            raise ValueError(f"center_pool: centres {tuple(c.shape)} for a clip of {lead[0]} x {lead[1]} ((B, T, 2) expected)")
+    n = c.shape[0] if clip is None else lead[0] * lead[1]
+    if out is None:
+        out = torch.zeros((n, max(p, 0), max(q, 0), 4), dtype=torch.float32, device=c.device)
+        coff = 0 if coff is None else coff
+    else:
+        _dev_ok(out)
+        if (out.dim() != 4 or tuple(out.shape[:3]) != (n, p, q) or out.dtype != torch.float32 or not out.is_contiguous()
+                or out.device != c.device):
+            raise ValueError(f"center_pool: `out` {tuple(out.shape)} {out.dtype} on {out.device}, a contiguous float32 "
+                             f"({n}, {p}, {q}, ld) on {c.device} expected")
+        if coff is None:
+            raise ValueError("center_pool: `coff` names the channel of `out` to write")
+    fn = _C.lib().up_center_pool if clip is None else _C.lib().up_clip_center_pool_flip if flip else _C.lib().up_clip_center_pool
+    _C.check(fn(c.data_ptr(), float(sigma), out.data_ptr(), out.shape[3], int(coff), *lead, h, w, p, q, _stream(out)), "center_pool")
+    return out
 
 
 DATASET_IDS = {"LSP": 0, "COCO": 1, "Penn_Action": 2, "NTID": 3, "PoseTrack": 4, "BBC": 5, "MPII": 6}

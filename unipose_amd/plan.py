@@ -119,6 +119,54 @@ class _Plan:
         from . import ops, protocol
         return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, self.bbox, pairs), self.out_channels)
 
+    def _frame_ws(self, program):
+        """a program from frames keeps the mirrored input through the first trunk: its own need, made at the first call (`_flip_ws`)"""
+        return self._ws(getattr(_C.lib(), self._prefix + "_program_workspace")(self._plan, _C.PROGRAM_FROM_FRAMES + program))
+
+    def _frame_args(self, who, frames, center, scale, frame_of, rot, valid_hw, lead=None):
+        """the arguments of up_crop_to_nhwc / up_clip_crop_to_nhwc as the entries from frames take them, and the tensors that must
+        outlive the call.  lead: the samples' leading shape, (batch,) by default, (B, T) for a clip."""
+        from . import protocol
+        name = type(self).__name__
+        lead = (self.batch,) if lead is None else tuple(lead)
+        n = 1
+        for d in lead:
+            n *= d
+        if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.device != self.device
+                or frames.dtype not in (torch.uint8, torch.float32)):
+            raise ValueError(f"{name}.{who}: frames (F, Hs, Ws, 3) uint8 or float32 on {self.device}, got "
+                             f"{tuple(frames.shape)} {frames.dtype} on {frames.device}")
+        x = frames.contiguous()
+        nf, hs, ws = x.shape[:3]
+        if len(lead) > 1 and center is not None and scale is not None:
+            import numpy as np
+            # a tensor stays one (protocol.get_transform keeps the reference's arithmetic in a tensor scale's dtype)
+            c = center if isinstance(center, torch.Tensor) else np.asarray(center)
+            sc = scale if isinstance(scale, torch.Tensor) else np.asarray(scale)
+            if tuple(c.shape) != lead + (2,) or tuple(sc.shape) != lead:
+                raise ValueError(f"{name}.{who}: center {tuple(c.shape)} / scale {tuple(sc.shape)}, one crop per frame is "
+                                 f"{lead + (2,)} / {lead}")
+            center, scale = c.reshape(n, 2), sc.reshape(n)
+        if center is None or scale is None or len(center) != n or len(scale) != n:
+            raise ValueError(f"{name}.{who}: one centre and one scale per sample of the batch of {n}")
+        m = torch.from_numpy(protocol.crop_maps(center, scale, [self.height, self.width], rot)).to(self.device)
+        fo = None
+        if frame_of is not None:
+            fo = torch.as_tensor(frame_of)
+            if tuple(fo.shape) != lead:
+                raise ValueError(f"{name}.{who}: frame_of {tuple(fo.shape)} for a batch of {lead}")
+            fo = fo.to(device=self.device, dtype=torch.int32).contiguous()
+        elif nf != n:
+            raise ValueError(f"{name}.{who}: {nf} frames for a batch of {n} and no frame_of")
+        valid = None
+        if valid_hw is not None:
+            valid = torch.as_tensor(valid_hw).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(valid.shape) != (nf, 2):
+                raise ValueError(f"{name}.{who}: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
+        args = (x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, hs, ws, None if fo is None else fo.data_ptr(),
+                None if valid is None else valid.data_ptr(), m.data_ptr(), 128.0, 128.0, 256.0)
+        return args, (x, m, fo, valid), (center, scale)
+
     def close(self):
         if self._plan:
             getattr(_C.lib(), self._prefix + "_destroy")(self._plan)
@@ -261,39 +309,6 @@ class UniPosePlan(_Plan):
         return preds, coords, maxvals
 
     # ---- from source frames: the crop (up_crop_to_nhwc) in front of the same programs ----------------------------------------------
-    def _frame_ws(self, program):
-        """a program from frames keeps the mirrored input through the first trunk: its own need, made at the first call (`_flip_ws`)"""
-        return self._ws(_C.lib().up_unipose_plan_program_workspace(self._plan, _C.PROGRAM_FROM_FRAMES + program))
-
-    def _frame_args(self, who, frames, center, scale, frame_of, rot, valid_hw):
-        """the arguments of up_crop_to_nhwc as the two entries take them, and the tensors that must outlive the call"""
-        from . import protocol
-        if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.device != self.device
-                or frames.dtype not in (torch.uint8, torch.float32)):
-            raise ValueError(f"UniPosePlan.{who}: frames (F, Hs, Ws, 3) uint8 or float32 on {self.device}, got "
-                             f"{tuple(frames.shape)} {frames.dtype} on {frames.device}")
-        x = frames.contiguous()
-        nf, hs, ws = x.shape[:3]
-        if center is None or scale is None or len(center) != self.batch or len(scale) != self.batch:
-            raise ValueError(f"UniPosePlan.{who}: one centre and one scale per sample of the batch of {self.batch}")
-        m = torch.from_numpy(protocol.crop_maps(center, scale, [self.height, self.width], rot)).to(self.device)
-        fo = None
-        if frame_of is not None:
-            fo = torch.as_tensor(frame_of)
-            if tuple(fo.shape) != (self.batch,):
-                raise ValueError(f"UniPosePlan.{who}: frame_of {tuple(fo.shape)} for a batch of {self.batch}")
-            fo = fo.to(device=self.device, dtype=torch.int32).contiguous()
-        elif nf != self.batch:
-            raise ValueError(f"UniPosePlan.{who}: {nf} frames for a batch of {self.batch} and no frame_of")
-        valid = None
-        if valid_hw is not None:
-            valid = torch.as_tensor(valid_hw).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(valid.shape) != (nf, 2):
-                raise ValueError(f"UniPosePlan.{who}: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
-        args = (x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, hs, ws, None if fo is None else fo.data_ptr(),
-                None if valid is None else valid.data_ptr(), m.data_ptr(), 128.0, 128.0, 256.0)
-        return args, (x, m, fo, valid)
-
     def frame_heatmaps(self, frames: torch.Tensor, center, scale, frame_of=None, rot=0, flip: bool = False, dataset: str = None,
                        pairs=None, valid_hw=None, out: torch.Tensor = None):
         """The heat-maps of persons in source frames in one call (``up_unipose_frame_heatmaps``): frames (F, Hs, Ws, 3) uint8 or
@@ -302,7 +317,7 @@ class UniPosePlan(_Plan):
         sampled as ``ops.crop_to_nhwc`` does (border = mean = 128, std = 256): no NCHW input is staged and each person reads the
         frame once.  Returns ONE (B, out_channels, h, w) tensor on the maps' own grid: equal bits to the plan's maps of the
         cropped input, with `flip` to ``flip_heatmaps`` of it (`dataset` / `pairs` as there)."""
-        args, keep = self._frame_args("frame_heatmaps", frames, center, scale, frame_of, rot, valid_hw)
+        args, keep, _ = self._frame_args("frame_heatmaps", frames, center, scale, frame_of, rot, valid_hw)
         perm = self._perm(dataset, pairs) if flip else None
         out = self._out("UniPosePlan.frame_heatmaps", out, (self.batch, self.out_channels, self.map_height, self.map_width))
         ws, nbytes = self._frame_ws(4 if flip else 0)
@@ -319,7 +334,7 @@ class UniPosePlan(_Plan):
         The way back is ``protocol.inverse_maps(center, scale, res)`` with `res` = [W, H] of the maps by default, as in
         ``final_preds``; a rotation is not undone on the way back, as in pytorch-pose (``transform_preds`` passes rot = 0)."""
         from . import protocol
-        args, keep = self._frame_args("frame_final_preds", frames, center, scale, frame_of, rot, valid_hw)
+        args, keep, _ = self._frame_args("frame_final_preds", frames, center, scale, frame_of, rot, valid_hw)
         perm = self._perm(dataset, pairs) if flip else None
         res = [self.map_width, self.map_height] if res is None else protocol._res(res)
         inv = torch.from_numpy(protocol.inverse_maps(center, scale, res)).to(self.device)
@@ -353,6 +368,8 @@ class UniPoseLSTMPlan(_Plan):
         preds, coords, maxvals = plan.clip_final_preds(x, cm, center, scale, flip=True, pairs=[[1, 2], [3, 4]])
         state = plan.stream_state()                                        # a camera: one frame in, joints out
         preds, maxvals, idx = plan.stream(frame, centermap, state, first=True)
+        preds, coords, maxvals = plan.clip_frame_final_preds(frames_u8_hwc, center, scale, frame_of=fo)    # the crop and the centre map too
+        preds, coords, maxvals = plan.stream_frames(frames_u8_hwc, center, scale, state, first=True)
 
     The state is the caller's, NCHW (B, K+2, h, w) as the reference's signature has it; the (K+2, h, w) zeros of the reference's
     first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
@@ -505,6 +522,13 @@ class UniPoseLSTMPlan(_Plan):
         off = (-buf.data_ptr()) % 256
         return buf[off:off + n]
 
+    def _check_state(self, who, state):
+        n = _C.lib().up_unipose_lstm_plan_state_bytes(self._plan)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or state.numel() != n
+                or state.device != self.device or not state.is_contiguous() or state.data_ptr() % 256):
+            raise ValueError(f"UniPoseLSTMPlan.{who}: `state` is not a buffer of stream_state() ({n} bytes, uint8, 256-byte aligned, "
+                             f"on {self.device})")
+
     def stream(self, frame: torch.Tensor, centermap: torch.Tensor, state: torch.Tensor, first: bool = False,
                full_resolution: bool = False, heat: torch.Tensor = None):
         """One frame in, joints out (``up_unipose_lstm_stream_keypoints``): (preds (B, K+1, 2), maxvals (B, K+1, 1), idx (B, K+1)
@@ -514,11 +538,7 @@ class UniPoseLSTMPlan(_Plan):
         B, H, W, h, w, K = self.batch, self.height, self.width, self.out_height, self.out_width, self.num_classes
         x = self._input(frame, (B, 3, H, W), "frame")
         cm = self._input(centermap, (B, 1, H, W), "centre map")
-        n = _C.lib().up_unipose_lstm_plan_state_bytes(self._plan)
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or state.numel() != n
-                or state.device != self.device or not state.is_contiguous() or state.data_ptr() % 256):
-            raise ValueError(f"UniPoseLSTMPlan.stream: `state` is not a buffer of stream_state() ({n} bytes, uint8, 256-byte aligned, "
-                             f"on {self.device})")
+        self._check_state("stream", state)
         if heat is not None:
             _check_out("UniPoseLSTMPlan.stream", "heat", heat, (B, K + 1, h, w), self.device)
         preds, maxvals, idx = self._outs("UniPoseLSTMPlan.stream", None, ("preds", "maxvals", "idx"),
@@ -530,3 +550,108 @@ class UniPoseLSTMPlan(_Plan):
                                                            None if heat is None else heat.data_ptr(), ws, nbytes, self._stream()),
                  "unipose_lstm_stream_keypoints")
         return preds, maxvals, idx
+
+    # ---- from source frames: the clip crop and the centre pool in front of the same programs ----------------------------------------
+    def _crop_center(self, who, crop_center, lead):
+        """the centre of the centre map per sample, (lead, 2) float64 on the device: [int(W / 2), int(H / 2)] by default, where
+        get_transform sends `center` (res / 2) and the reference's video loader puts it (penn_action_data.py:105-106,130)"""
+        if crop_center is None:
+            c = torch.tensor([float(int(self.width / 2)), float(int(self.height / 2))], dtype=torch.float64)
+            return c.expand(*lead, 2).contiguous().to(self.device)
+        if not isinstance(crop_center, torch.Tensor):
+            import numpy as np
+            crop_center = np.ascontiguousarray(crop_center, dtype=np.float64)
+        c = torch.as_tensor(crop_center, dtype=torch.float64)
+        if tuple(c.shape) == (2,):
+            c = c.expand(*lead, 2)
+        if tuple(c.shape) != tuple(lead) + (2,):
+            raise ValueError(f"UniPoseLSTMPlan.{who}: crop_center {tuple(c.shape)}, (2,) or {tuple(lead) + (2,)} expected")
+        return c.contiguous().to(self.device)
+
+    def clip_frame_heatmaps(self, frames: torch.Tensor, center, scale, frame_of=None, rot=0, flip: bool = False, pairs=None,
+                            dataset: str = None, valid_hw=None, crop_center=None, sigma: float = 3.0, out=None):
+        """The heat-maps of a clip from source frames in one call (``up_unipose_lstm_clip_frame_heatmaps``): frames (F, Hs, Ws, 3)
+        uint8 or float32 on the device, `center` (B, T, 2) / `scale` (B, T) one crop per frame of the clip, frame_of (B, T) the
+        source frame each reads (None: sample (b, t) reads frame b * T + t).  The crop maps are ``protocol.crop_maps`` of the
+        flattened (B * T) centres and scales, sampled as ``ops.clip_crop_to_nhwc`` does; the centre map is never built: its pooled
+        form comes from `crop_center` ((B, T, 2) or (2,), in pixels of the network input; default [int(W / 2), int(H / 2)], where the
+        crop puts `center`) and `sigma` (``ops.center_pool``).  Returns (heats (B, T, K+1, h, w), cell, hide (B, K+2, h, w) of the
+        last frame) — equal bits to ``clip`` of the cropped clip and ``ops.make_centermaps(crop_center, H, W, sigma)`` — or with
+        `flip` ONE (B, T, K+1, h, w) tensor, equal bits to ``clip_flip_heatmaps`` (`pairs` / `dataset` as there; `out` is then that
+        tensor, else the triple)."""
+        B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
+        args, keep, _ = self._frame_args("clip_frame_heatmaps", frames, center, scale, frame_of, rot, valid_hw, (B, T))
+        cc = self._crop_center("clip_frame_heatmaps", crop_center, (B, T))
+        L = _C.lib()
+        if flip:
+            perm = self._perm(dataset, pairs)
+            heat = self._out("UniPoseLSTMPlan.clip_frame_heatmaps", out, (B, T, K + 1, h, w))
+            ws, nbytes = self._frame_ws(4)
+            _C.check(L.up_unipose_lstm_clip_frame_heatmaps(self._plan, *args, cc.data_ptr(), float(sigma), perm, heat.data_ptr(), None,
+                                                           None, ws, nbytes, self._stream()), "unipose_lstm_clip_frame_heatmaps")
+            del keep
+            return heat
+        heat, cell, hide = self._outs("UniPoseLSTMPlan.clip_frame_heatmaps", out, ("heat", "cell", "hide"),
+                                      [(B, T, K + 1, h, w), (B, K + 2, h, w), (B, K + 2, h, w)])
+        ws, nbytes = self._frame_ws(2)
+        _C.check(L.up_unipose_lstm_clip_frame_heatmaps(self._plan, *args, cc.data_ptr(), float(sigma), None, heat.data_ptr(),
+                                                       cell.data_ptr(), hide.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_lstm_clip_frame_heatmaps")
+        del keep
+        return heat, cell, hide
+
+    def clip_frame_final_preds(self, frames: torch.Tensor, center, scale, frame_of=None, rot=0, flip: bool = False, pairs=None,
+                               dataset: str = None, valid_hw=None, crop_center=None, sigma: float = 3.0, res=None, out=None):
+        """Frames, centres and scales in, the clip's joints in frame pixels out (``up_unipose_lstm_clip_frame_final_preds``): the
+        crop and the centre pool of ``clip_frame_heatmaps``, the network (with `flip` the flip test), then ``final_preds`` — (preds
+        (B, T, K+1, 2) in source-frame pixels, coords (B, T, K+1, 2) on the heat-map grid, maxvals (B, T, K+1, 1)), equal bits to
+        ``clip_final_preds`` of the cropped clip.  The way back is ``protocol.inverse_maps(center, scale, res)`` per frame with `res`
+        = [w, h] of the maps by default, as in ``clip_final_preds``; a rotation is not undone on the way back."""
+        from . import protocol
+        B, T, h, w, K = self.batch, self.frames, self.out_height, self.out_width, self.num_classes
+        args, keep, (c, sc) = self._frame_args("clip_frame_final_preds", frames, center, scale, frame_of, rot, valid_hw, (B, T))
+        cc = self._crop_center("clip_frame_final_preds", crop_center, (B, T))
+        perm = self._perm(dataset, pairs) if flip else None
+        res = [w, h] if res is None else protocol._res(res)
+        if int(res[0]) <= 0 or int(res[1]) <= 0:
+            raise ValueError(f"UniPoseLSTMPlan.clip_frame_final_preds: res {list(res)}")
+        inv = torch.from_numpy(protocol.inverse_maps(c, sc, res)).to(self.device)
+        shapes = ((B, T, K + 1, 2), (B, T, K + 1, 2), (B, T, K + 1, 1))
+        preds, coords, maxvals = self._outs("UniPoseLSTMPlan.clip_frame_final_preds", out, ("preds", "coords", "maxvals"), shapes,
+                                            word="tuple")
+        ws, nbytes = self._frame_ws(5 if flip else 6)
+        _C.check(_C.lib().up_unipose_lstm_clip_frame_final_preds(self._plan, *args, cc.data_ptr(), float(sigma), perm, inv.data_ptr(),
+                                                                 int(res[0]), int(res[1]), preds.data_ptr(), coords.data_ptr(),
+                                                                 maxvals.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_lstm_clip_frame_final_preds")
+        del keep
+        return preds, coords, maxvals
+
+    def stream_frames(self, frames: torch.Tensor, center, scale, state: torch.Tensor, first: bool = False, frame_of=None, rot=0,
+                      valid_hw=None, crop_center=None, sigma: float = 3.0, res=None, heat: torch.Tensor = None):
+        """One camera frame in, joints in frame pixels out (``up_unipose_lstm_stream_frame_final_preds``): frames (F, Hs, Ws, 3),
+        `center` (B, 2) / `scale` (B,) one person per sample, frame_of (B,) as in ``UniPosePlan.frame_final_preds``; the crop, the
+        centre pool (`crop_center` (B, 2) or (2,), `sigma`), the step of ``stream`` with hide and cell kept in `state`
+        (``stream_state()``; first: the first frame of a stream), then ``final_preds``: (preds (B, K+1, 2) in source-frame pixels,
+        coords (B, K+1, 2), maxvals (B, K+1, 1)) — equal bits to ``ops.final_preds`` of ``stream``'s heat-maps of the cropped frame.
+        `heat`: an optional (B, K+1, h, w) tensor that receives the NCHW heat-maps; it is then returned as a fourth item."""
+        from . import protocol
+        B, h, w, K = self.batch, self.out_height, self.out_width, self.num_classes
+        args, keep, (c, sc) = self._frame_args("stream_frames", frames, center, scale, frame_of, rot, valid_hw)
+        cc = self._crop_center("stream_frames", crop_center, (B,))
+        self._check_state("stream_frames", state)
+        if heat is not None:
+            _check_out("UniPoseLSTMPlan.stream_frames", "heat", heat, (B, K + 1, h, w), self.device)
+        res = [w, h] if res is None else protocol._res(res)
+        if int(res[0]) <= 0 or int(res[1]) <= 0:
+            raise ValueError(f"UniPoseLSTMPlan.stream_frames: res {list(res)}")
+        inv = torch.from_numpy(protocol.inverse_maps(c, sc, res)).to(self.device)
+        preds, coords, maxvals = self._outs("UniPoseLSTMPlan.stream_frames", None, ("preds", "coords", "maxvals"),
+                                            ((B, K + 1, 2), (B, K + 1, 2), (B, K + 1, 1)))
+        ws, nbytes = self._frame_ws(7 if first else 8)
+        _C.check(_C.lib().up_unipose_lstm_stream_frame_final_preds(
+            self._plan, *args, cc.data_ptr(), float(sigma), state.data_ptr(), int(bool(first)), inv.data_ptr(), int(res[0]), int(res[1]),
+            preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), None if heat is None else heat.data_ptr(), ws, nbytes,
+            self._stream()), "unipose_lstm_stream_frame_final_preds")
+        del keep
+        return (preds, coords, maxvals) if heat is None else (preds, coords, maxvals, heat)
