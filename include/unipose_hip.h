@@ -161,7 +161,10 @@ int up_conv_tune(const char* key, int value);
 /* Diagnostics: fp32 forward / data-gradient launches since load, by kernel family ("big": bf16-storage launches on igemm_big_kernel) — "igemm" (register-staged igemm_kernel),
  * "glds32" (f32_glds.h), "glds32_epi1" (of those, with the LDS-transposed epilogue), "glds32_bnred" (with the fused
  * BatchNorm-backward reduction), "wgrad_glds32" / "wgrad_glds32_st1" (fp32 weight-gradient launches on the direct-to-LDS kernel /
- * of those, the one-stage form); -1 for an unknown name.  Tests use it to prove which kernel a case ran on. */
+ * of those, the one-stage form), "wgrad_rect" (weight-gradient launches of any family that ran with a live-rectangle table),
+ * "wgrad_st1" (register-staged fp32 weight-gradient launches on the one-stage form); two names are not counts but describe the most
+ * recent weight-gradient launch: "wgrad_splits" (its pixel splits) and "wgrad_variant" (its index for up_profile_variant_name: kernel
+ * family and tile pair, also where nothing is profiled; -1 before the first launch); -1 for an unknown name.  Tests use it to prove which kernel a case ran on. */
 long long up_conv_counter(const char* name);
 /* Analysis (host only, no launch): share of (row tile, filter tap) pairs the K loop of the forward (data_gradient = 0) or
  * data-gradient launch of `d` visits with its rows in image order and in tap-sorted order ("tap_sort" knob), and the share

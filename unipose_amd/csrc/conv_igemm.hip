@@ -2018,6 +2018,8 @@ static int g_big_stages = env_int("UP_BIG_STAGES", 3, 2);   // LDS stages of the
 static long long g_count_igemm = 0, g_count_glds32 = 0, g_count_glds32_epi1 = 0, g_count_glds32_bnred = 0;   // up_conv_counter
 static long long g_count_big = 0;   // launches on igemm_big_kernel (bf16s_big.h)
 static long long g_count_wgrad32 = 0, g_count_wgrad32_st1 = 0, g_count_glds32_wide = 0, g_count_glds32_grouped = 0;
+static long long g_count_wgrad_rect = 0, g_count_wgrad_st1 = 0;   // weight-gradient launches with a rectangle table / register-staged on one stage
+static long long g_wgrad_last_splits = 0, g_wgrad_last_variant = -1;   // pixel splits and profile variant (kVariantNames) of the latest weight-gradient launch
 static thread_local bool g_extras_dropped = false;   // (per host thread: autograd runs one thread per device) a launch was asked for a masked addend / fused reduction on a kernel without them
 static int g_glds32 = env_int("UP_GLDS32", 1, 0);
 static int g_glds32_epi = env_int("UP_GLDS32_EPI", 1, 0);
@@ -2661,6 +2663,10 @@ extern "C" long long up_conv_counter(const char* name) {
     if (!strcmp(name, "stem7")) return g_count_stem7;
     if (!strcmp(name, "wgrad_glds32")) return g_count_wgrad32;
     if (!strcmp(name, "wgrad_glds32_st1")) return g_count_wgrad32_st1;
+    if (!strcmp(name, "wgrad_rect")) return g_count_wgrad_rect;
+    if (!strcmp(name, "wgrad_splits")) return g_wgrad_last_splits;
+    if (!strcmp(name, "wgrad_variant")) return g_wgrad_last_variant;
+    if (!strcmp(name, "wgrad_st1")) return g_count_wgrad_st1;
     return -1;
 }
 
@@ -3479,6 +3485,15 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
     size_t need = (size_t)p.splits * d->K * d->R * d->S * d->Cp * sizeof(float);
     UP_REQUIRE(workspace_bytes >= need, UP_ERR_WORKSPACE, "conv2d_bwd_weight: workspace %zu < %zu", workspace_bytes,
                need);
+    // the bias gradient's partial rows lie behind the slabs: refused here, before anything is launched (dw is still untouched,
+    // and under `accumulate` a retry does not add the gradient twice)
+    const bool quads = d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
+    const int rpb = quads ? 256 : 1024;
+    const size_t off = (need + 63) / 64 * 64;
+    const int bias_rows = cdiv((int64_t)d->N * d->P * d->Q, rpb);
+    UP_REQUIRE(!dbias || workspace_bytes >= off + (size_t)bias_rows * d->K * sizeof(float), UP_ERR_WORKSPACE,
+               "conv2d_bwd_weight: workspace %zu too small for the bias gradient's partial rows (%zu)", workspace_bytes,
+               off + (size_t)bias_rows * d->K * sizeof(float));
     hipStream_t st = as_stream(stream);
     WgradArgs a;
     memset(&a, 0, sizeof(a));
@@ -3509,6 +3524,7 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
     a.fTiles = make_fastdiv(p.ntm * p.ntn);
     a.nwg = p.ntm * p.ntn * p.splits;
     dim3 grid(a.nwg);
+    g_wgrad_last_splits = p.splits;
     // bf16-operand form (BASELINE configs[4] arithmetic): 32-bit element offsets inside the kernel
     const bool use_bf16 = bf16 && (int64_t)d->N * d->H * d->W * d->ldx < (1ll << 31) &&
                           (int64_t)d->N * d->P * d->Q * d->ldy < (1ll << 31);
@@ -3517,9 +3533,11 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
         const long long xb = (long long)d->N * d->H * d->W * d->ldx * 2, dyb = (long long)d->N * d->P * d->Q * d->ldy * 2;
         const bool glds_form = bf16 == 2 && g_glds && xb < (1ll << 31) && dyb < (1ll << 31) &&
                                ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0;
+        g_wgrad_last_variant = glds_form ? v + 8 : v;
         ProfScope prof(glds_form ? v + 8 : v, 2.0 * (double)a.M * (double)d->K * (double)d->R * d->S * d->C, st, d->K, a.Ncols, a.M,
                        a.nwg);
         a.rect = (g_wgrad_rect && (int64_t)d->N * d->P * d->Q < (1ll << 30)) ? wgrad_rect_device(d, p) : nullptr;
+        if (a.rect) ++g_count_wgrad_rect;
         if (glds_form) {
             // second generation (bf16s_glds.h): [pixel][channel] slices HBM -> LDS directly, transposing fragment reads
             a.x_bytes = (uint32_t)xb;
@@ -3556,12 +3574,14 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
 #ifdef UP_PROBE
         glds32_form = glds32_form && !g_wgrad_single && !g_wgrad_dbg;
 #endif
+        g_wgrad_last_variant = glds32_form ? v + 24 : v;
         ProfScope prof(glds32_form ? v + 24 : v, 2.0 * (double)a.M * (double)d->K * (double)d->R * d->S * d->C, st, d->K, a.Ncols,
                        a.M, a.nwg);
         if (glds32_form) {
             a.x_bytes = (uint32_t)xb;
             a.dy_bytes = (uint32_t)dyb;
             a.rect = g_wgrad_rect ? wgrad_rect_device(d, p) : nullptr;
+            if (a.rect) ++g_count_wgrad_rect;
             const bool single = a.nwg > 2 * cu_count();   // (wgrad_kernel's rule: one LDS stage when more than two workgroups per CU queue up)
             ++g_count_wgrad32;
             if (single) ++g_count_wgrad32_st1;
@@ -3602,6 +3622,8 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
             // (probe, 3x3 512->512: 115 vs 104 TFLOP/s; in the network the double buffer is 0.5 % faster overall)
             const bool single = a.nwg > 2 * cu_count();
             a.rect = (g_wgrad_rect && (int64_t)d->N * d->P * d->Q < (1ll << 30)) ? wgrad_rect_device(d, p) : nullptr;
+            if (a.rect) ++g_count_wgrad_rect;
+            if (single) ++g_count_wgrad_st1;
             if (a.rect && single) {
                 if (p.bm == 128 && p.bn == 128)
                     hipLaunchKernelGGL((wgrad_kernel<128, 128, 64, true>), grid, dim3(256), 0, st, a);
@@ -3643,12 +3665,7 @@ static int up::conv2d_bwd_weight_impl(const up_conv_desc* d, const float* x, con
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total4, 256)), dim3(256), 0, st, (const float*)workspace, dw,
                        p.splits, d->K, d->C, d->Cp, d->R * d->S, total4, accumulate);
     if (dbias) {
-        const bool quads = d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-        const int rpb = quads ? 256 : 1024;
-        dim3 g(cdiv(a.M, rpb), cdiv(d->K, 64));
-        const size_t off = (need + 63) / 64 * 64;
-        UP_REQUIRE(workspace_bytes >= off + (size_t)g.x * d->K * sizeof(float), UP_ERR_WORKSPACE,
-                   "conv2d_bwd_weight: workspace %zu too small for the bias gradient's partial rows", workspace_bytes);
+        dim3 g(bias_rows, cdiv(d->K, 64));
         float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + off);
         if (quads && bf16 == 2)
             hipLaunchKernelGGL(colsum4_kernel<bf16_t>, g, dim3(256), 0, st, reinterpret_cast<const bf16_t*>(dy), d->ldy,
