@@ -787,7 +787,17 @@ int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int
  * Refused before anything is launched: what up_crop_to_nhwc refuses, and what the entries above refuse.  The mirrored input stays
  * alive through the first trunk, so the flip forms need more than up_unipose_plan_flip_workspace(): the need of each is
  * up_unipose_plan_program_workspace(plan, UP_PROGRAM_FROM_FRAMES + k), k = 0, 4, 5, 6 naming the program it otherwise equals (0 for
- * any other k); neither up_unipose_plan_workspace() nor up_unipose_plan_flip_workspace() changes. */
+ * any other k); neither up_unipose_plan_workspace() nor up_unipose_plan_flip_workspace() changes.
+ * Storage: up_unipose_plan_create_t(cfg, dtype, &plan) with dtype = UP_DT_F32 (what up_unipose_plan_create makes) or UP_DT_BF16;
+ * any other dtype is UP_ERR_INVALID, *plan stays untouched and nothing is allocated.  up_unipose_plan_dtype() reads it back.  A
+ * UP_DT_BF16 plan runs every program above in bf16 STORAGE: the launches of the folded module under the bf16-storage arithmetic
+ * (UP_MATH_BF16S).  The input pass (layout or crop) and backbone.conv1 stay fp32 (4 input channels are no multiple of 32), the
+ * stem's max-pool writes bf16 (up_maxpool3s2_fwd_t), every later convolution is up_conv2d_fwd_bf16(UP_MATH_BF16S) on bf16 tensors
+ * whose channels are padded to multiples of 32 (pad lanes zeroed by the program in every call), the pooling, resize and concat
+ * passes are the `_t` forms, and decoder.last_conv.8 is the UP_MATH_BF16S_F32OUT launch: the endings read fp32 NHWC maps of
+ * out_channels rounded up to 32 lanes.  The plan keeps bf16 weight images (the hi plane of up_pack_weights_bf16; fp32 for the
+ * stem) and fp32 biases.  Nothing changes at the boundary: fp32 input or source frames, fp32 results, folded fp32 OIHW weights
+ * through up_unipose_plan_set_conv, the same refusals.  The workspace figures are the plan's own (smaller than the fp32 plan's). */
 enum { UP_PROGRAM_FROM_FRAMES = 256 };
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
@@ -795,7 +805,9 @@ typedef struct {
     int32_t output_stride;          /* 16 or 8 (resnet.py:49-58) */
     int32_t out_channels;           /* channels of decoder.last_conv.8: num_classes + 1 (+ 5 for the multi-person box head) */
 } up_unipose_config;
-int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** plan);
+int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** plan);     /* = ..._create_t(cfg, UP_DT_F32, plan) */
+int up_unipose_plan_create_t(const up_unipose_config* cfg, int dtype, up_unipose_plan** plan);
+int up_unipose_plan_dtype(const up_unipose_plan* plan);      /* UP_DT_F32 / UP_DT_BF16; UP_ERR_INVALID for NULL */
 void up_unipose_plan_destroy(up_unipose_plan* plan);
 int up_unipose_plan_num_convs(const up_unipose_plan* plan);
 const char* up_unipose_plan_conv_name(const up_unipose_plan* plan, int i);

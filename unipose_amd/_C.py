@@ -157,6 +157,8 @@ SIGNATURES = {
     "up_box_argmax": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "up_persons_decode": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "up_unipose_plan_create": (_i, [_p, C.POINTER(_p)]),
+    "up_unipose_plan_create_t": (_i, [_p, _i, C.POINTER(_p)]),
+    "up_unipose_plan_dtype": (_i, [_p]),
     "up_unipose_plan_destroy": (None, [_p]),
     "up_unipose_plan_num_convs": (_i, [_p]),
     "up_unipose_plan_conv_name": (C.c_char_p, [_p, _i]),

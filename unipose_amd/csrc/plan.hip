@@ -11,6 +11,9 @@
 // The launches, their order, their descriptors and their epilogues are exactly those of the drop-in modules' folded inference
 // forwards (unipose_amd/unipose.py, uniposeLSTM.py + modules.py after checkpoint.load_folded), so the two produce equal bits
 // (tests/test_plan_*.py, tests/test_lstm_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
+// The image plan also runs in bf16 STORAGE (up_unipose_plan_create_t with UP_DT_BF16): the same programs with bf16 tensors and
+// weight images behind the fp32 stem, the launches of the folded module under ops.set_conv_math("bf16s") — equal bits again
+// (tests/test_plan_bf16_*.py).  The element type is a parameter of trunk() and of the weight store; the video plan passes fp32.
 //
 // What the file holds, top to bottom:
 //   Plan        one program: tensors, convolutions, ops, and the first-fit workspace layout over the tensors' live ranges
@@ -52,23 +55,26 @@ static void dev_free(void* p) {
 }
 
 static inline int rup4(int c) { return (c + 3) / 4 * 4; }
+static inline int rup32(int c) { return (c + 31) / 32 * 32; }
 
 struct Tensor {
     int n, h, w, c;        // NHWC, c = physical channels
+    size_t elem;           // bytes per element: 4 fp32, 2 bf16 (bf16 storage), 1 the max-pool's index tensor
     size_t bytes;
     int first = -1, last = -1;
     size_t off = 0;
 };
 struct Ref {
     int id = -1;
-    size_t elems = 0;      // element offset inside the tensor (row slices of the stacked WASP branches)
+    size_t elems = 0;      // offset inside the tensor in ITS elements (row slices of the stacked WASP branches)
 };
 struct Conv {
     std::string name;      // state_dict prefix: <name>.weight (+ <name>.bias after folding)
     up_conv_desc d;
     int relu;
     bool has_bias;         // the folded network has a bias on every convolution but wasp.conv2
-    float* w_fwd = nullptr;   // the plan's store of that name (Weights::bind)
+    int math = UP_MATH_F32;   // UP_MATH_F32: up_conv2d_fwd; UP_MATH_BF16S / UP_MATH_BF16S_F32OUT: up_conv2d_fwd_bf16 on bf16 tensors
+    float* w_fwd = nullptr;   // the plan's store of that name (Weights::bind): the fp32 image, or the bf16 hi plane
     float* bias = nullptr;
 };
 // one Kind per C function called (STATE_IN / STATE_OUT: up_copy2d from / to the caller's state buffer)
@@ -99,10 +105,15 @@ struct Plan {
     std::vector<Conv> convs;
     std::vector<Op> ops;
     size_t ws_bytes = 0;
+    // layout(): let the free block under the top grow into a tensor that fits nowhere.  The bf16 image plan sets it: its largest
+    // tensor is the up-sampled fp32 maps at the end of program 1 (rup32 lanes), larger than anything the bf16 trunk leaves free.
+    // The fp32 plans keep the layout, and so the workspace figures, they always had.
+    bool grow_tail = false;
 
     int tensor(int n, int h, int w, int c, size_t elem = 4) {
         Tensor t;
         t.n = n; t.h = h; t.w = w; t.c = c;
+        t.elem = elem;
         t.bytes = ((size_t)n * h * w * c * elem + 255) / 256 * 256;
         tensors.push_back(t);
         return (int)tensors.size() - 1;
@@ -121,9 +132,13 @@ struct Plan {
         touch(op.aux);
         ops.push_back(op);
     }
-    // conv (+ folded-BatchNorm bias) (+ residual) (+ ReLU) of `images` images at (h, w) with cp physical input channels
+    // conv (+ folded-BatchNorm bias) (+ residual) (+ ReLU) of `images` images at (h, w) with cp physical input channels.  The
+    // kernels follow the tensor's type (ops.conv_fwd_raw): a bf16 input runs up_conv2d_fwd_bf16 in bf16 storage and the output is
+    // padded to a multiple of 32 channels (ops.make_desc); f32out: the network's last convolution, bf16 in, fp32 out.  A padded
+    // output the plan makes itself is zeroed first, as the module allocates it: the launch writes lanes [0, K) only.
     Ref conv(const std::string& name, Ref x, int images, int h, int w, int cp, int c, int k, int r, int stride, int pad, int dil,
-             int relu, bool has_bias, Ref res = Ref(), Ref out = Ref()) {
+             int relu, bool has_bias, Ref res = Ref(), Ref out = Ref(), bool f32out = false) {
+        const bool b16 = tensors[x.id].elem == 2;
         Conv cv;
         cv.name = name;
         cv.relu = relu;
@@ -134,9 +149,13 @@ struct Plan {
         d.K = k; d.R = r; d.S = r; d.stride = stride; d.pad = pad; d.dil = dil;
         d.P = (h + 2 * pad - dil * (r - 1) - 1) / stride + 1;
         d.Q = (w + 2 * pad - dil * (r - 1) - 1) / stride + 1;
-        d.Kp = rup4(k);
+        d.Kp = b16 ? rup32(k) : rup4(k);
         d.ldy = d.Kp;
-        if (out.id < 0) out.id = tensor(images, d.P, d.Q, d.ldy);
+        cv.math = !b16 ? UP_MATH_F32 : f32out ? UP_MATH_BF16S_F32OUT : UP_MATH_BF16S;
+        if (out.id < 0) {
+            out.id = tensor(images, d.P, d.Q, d.ldy, b16 && !f32out ? 2 : 4);
+            if (b16 && d.ldy != k) zero(out);
+        }
         convs.push_back(cv);
         Op op;
         op.kind = CONV;
@@ -146,19 +165,20 @@ struct Plan {
         return out;
     }
     // an op from a tensor into a new one of out_h x out_w and as many channels: the two poolings and the bilinear resize
-    Ref resample(Kind kind, Ref in, int out_h, int out_w, size_t res_elem = 0) {
+    // (out_elem: the element size of the result where it is not the input's)
+    Ref resample(Kind kind, Ref in, int out_h, int out_w, size_t res_elem = 0, size_t out_elem = 0) {
         const Tensor t = tensors[in.id];
         Op op;
         op.kind = kind;
         op.in = in;
-        op.out.id = tensor(t.n, out_h, out_w, t.c);
+        op.out.id = tensor(t.n, out_h, out_w, t.c, out_elem ? out_elem : t.elem);
         if (res_elem) op.res.id = tensor(t.n, out_h, out_w, t.c, res_elem);
         op.n = t.n;
         push(op);
         return op.out;
     }
-    Ref maxpool(Ref in) {      // 3x3 stride 2 with its uint8 index tensor
-        return resample(MAXPOOL, in, (tensors[in.id].h - 1) / 2 + 1, (tensors[in.id].w - 1) / 2 + 1, 1);
+    Ref maxpool(Ref in, size_t out_elem = 0) {      // 3x3 stride 2 with its uint8 index tensor
+        return resample(MAXPOOL, in, (tensors[in.id].h - 1) / 2 + 1, (tensors[in.id].w - 1) / 2 + 1, 1, out_elem);
     }
     void zero(Ref t) {
         Op op;
@@ -194,9 +214,14 @@ struct Plan {
                         placed = true;
                         break;
                     }
-                if (!placed) {
+                if (!placed) {       // no free block holds it: at the top; grow_tail: from the start of a free block that ends there
                     T.off = top;
-                    top += T.bytes;
+                    for (Block& b : free_list)
+                        if (grow_tail && b.bytes && b.off + b.bytes == top) {
+                            T.off = b.off;
+                            b.bytes = 0;
+                        }
+                    top = T.off + T.bytes;
                 }
             }
             for (int t = 0; t < (int)tensors.size(); ++t) {
@@ -238,7 +263,12 @@ static Ref bottleneck(Plan& p, const std::string& name, Ref x, int n, int& h, in
 // waspVideo.py:56-59, whose global-average-pool branch has no BatchNorm (a convolution without bias), and the heat-map tensor
 // zeroed before the last convolution writes it: its spare pad channel is where the centre map goes (uniposeLSTM.py _AddCenter),
 // and the ConvLSTM gate convolution reads every physical channel.
-static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int out_channels, bool video) {
+// dt: the storage behind the stem (UP_DT_F32 / UP_DT_BF16).  In bf16 storage the launches are those of the folded module under
+// ops.set_conv_math("bf16s"): the stem stays fp32 (4 input channels: no multiple of 32), its max-pool writes bf16
+// (modules.ResNet.forward), every tensor behind it is bf16 with convolution outputs padded to 32 channels, and the last
+// convolution writes fp32 maps of rup32(out_channels) channels (modules.Decoder.forward, out_f32).  The video plan passes fp32.
+static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int out_channels, bool video, int dt) {
+    const size_t elem = dt == UP_DT_BF16 ? 2 : 4;
     int strides[4], dils[4];
     if (output_stride == 16) {
         const int s[4] = {1, 2, 2, 1}, d[4] = {1, 1, 1, 2};
@@ -251,7 +281,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     }
     // stem: 7x7 s2 + folded bn1 + ReLU, 3x3 s2 max-pool (resnet.py:113-117)
     x = p.conv("backbone.conv1", x, n, h, w, 4, 3, 64, 7, 2, 3, 1, 1, true);
-    x = p.maxpool(x);
+    x = p.maxpool(x, elem);
     h = p.tensors[x.id].h;
     w = p.tensors[x.id].w;
     // layer1..4 (resnet.py:76-111): (3, 4, 23, 3) blocks, multi-grid (1, 2, 4) in layer4
@@ -279,7 +309,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     const int wd[4] = {output_stride == 16 ? 24 : 48, output_stride == 16 ? 18 : 36, output_stride == 16 ? 12 : 24,
                        output_stride == 16 ? 6 : 12};
     Ref stack;
-    stack.id = p.tensor(4 * n, h, w, 256);
+    stack.id = p.tensor(4 * n, h, w, 256, elem);
     const size_t branch = (size_t)n * h * w * 256;
     Ref b1 = stack, b2 = stack, b3 = stack, b4 = stack;
     b2.elems = branch;
@@ -296,7 +326,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     g = p.conv("wasp.global_avg_pool.1", g, n, 1, 1, 2048, 2048, 256, 1, 1, 0, 1, 1, !video);
     g = p.resample(BILINEAR, g, h, w);
     Ref cat;
-    cat.id = p.tensor(n, h, w, 1280);
+    cat.id = p.tensor(n, h, w, 1280, elem);
     for (int i = 0; i < 4; ++i) {
         Ref s = y;
         s.elems = i * branch;
@@ -310,10 +340,11 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     const int dh = p.tensors[lw.id].h, dw = p.tensors[lw.id].w;
     x = p.resample(BILINEAR, x, dh, dw);
     Ref cat2;
-    cat2.id = p.tensor(n, dh, dw, 320);      // 256 + 48 = 304 real channels, zero-padded to a multiple of 32
-    p.zero(cat2);
+    cat2.id = p.tensor(n, dh, dw, 320, elem);      // 256 + 48 = 304 real channels, zero-padded to a multiple of 32
+    const int lc = p.tensors[lw.id].c;       // 48; in bf16 storage 64 physical channels, the pad lanes zeros: they fill cat2
+    if (256 + lc < 320) p.zero(cat2);
     p.copy(x, 256, cat2, 320, 0, (int64_t)n * dh * dw, 256);
-    p.copy(lw, 48, cat2, 320, 256, (int64_t)n * dh * dw, 48);
+    p.copy(lw, lc, cat2, 320, 256, (int64_t)n * dh * dw, lc);
     x = p.conv("decoder.last_conv.0", cat2, n, dh, dw, 320, 304, 256, 3, 1, 1, 1, 1, true);
     x = p.conv("decoder.last_conv.4", x, n, dh, dw, 256, 256, 256, 3, 1, 1, 1, 1, true);
     Ref heat;
@@ -323,7 +354,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     }
     h = dh;
     w = dw;
-    return p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, out_channels, 1, 1, 0, 1, 0, true, Ref(), heat);
+    return p.conv("decoder.last_conv.8", x, n, dh, dw, 256, 256, out_channels, 1, 1, 0, 1, 0, true, Ref(), heat, dt == UP_DT_BF16);
 }
 
 // ---- what a program is made of ---------------------------------------------------------------------------------------------------
@@ -405,10 +436,11 @@ static size_t program_workspace(const Program (&table)[N], const Plan* prog, int
     return 0;
 }
 
-static void build(Plan& p, const up_unipose_config& c, const Program& g) {
+static void build(Plan& p, const up_unipose_config& c, const Program& g, int dt) {
     const int n = c.batch;
     int h = c.height, w = c.width;
     const bool frames = g.input == IN_FRAMES;
+    p.grow_tail = dt == UP_DT_BF16;
     // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC); from frames: the crop writes NHWC itself, and the mirror beside it
     Ref x, m;
     x.id = p.tensor(n, h, w, 4);
@@ -420,7 +452,7 @@ static void build(Plan& p, const up_unipose_config& c, const Program& g) {
     op.ext = X;
     op.n = n; op.ch = 3;
     p.push(op);
-    x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false);
+    x = trunk(p, x, n, h, w, c.output_stride, c.out_channels, false, dt);
     if (g.flip) {
         int h2 = c.height, w2 = c.width;
         if (!frames) {
@@ -432,7 +464,7 @@ static void build(Plan& p, const up_unipose_config& c, const Program& g) {
             op.n = n; op.ch = 3;
             p.push(op);
         }
-        m = trunk(p, m, n, h2, w2, c.output_stride, c.out_channels, false);
+        m = trunk(p, m, n, h2, w2, c.output_stride, c.out_channels, false, dt);
         op = Op();
         op.kind = MERGE;                         // straight into the caller's NCHW tensor, or ...
         op.in = x; op.aux = m;
@@ -482,7 +514,7 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
         op.n = B; op.frames = T; op.ch = 3;
         p.push(op);
     }
-    Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true);
+    Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true, UP_DT_F32);
     // _AddCenter: the pooled centre map in the heat-maps' spare pad channel; (K + 1) % 4 == 0: a hand-over tensor of rup4(K + 2)
     // channels, zeros, the heat-maps copied in
     Ref z = heat;
@@ -664,9 +696,10 @@ struct Io {
 };
 
 static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, const char* what) {
-    auto ptr = [&](const Ref& r) -> float* {
-        return r.id < 0 ? nullptr : reinterpret_cast<float*>(ws + p.tensors[r.id].off) + r.elems;
+    auto ptr = [&](const Ref& r) -> float* {      // (a bf16 tensor travels through the same pointer arguments)
+        return r.id < 0 ? nullptr : reinterpret_cast<float*>(ws + p.tensors[r.id].off + r.elems * p.tensors[r.id].elem);
     };
+    auto dt = [](const Tensor& t) { return t.elem == 2 ? UP_DT_BF16 : UP_DT_F32; };
     static const Tensor none = {};
     for (const Op& op : p.ops) {
         // the tensors the op names, and the batch stride of NHWC maps read in place
@@ -686,22 +719,28 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             ep.residual = ptr(op.res);
             ep.ldr = op.res.id >= 0 ? p.tensors[op.res.id].c : 0;
             ep.relu = cv.relu;
-            e = up_conv2d_fwd(&cv.d, ptr(op.in), cv.w_fwd, ptr(op.out), &ep, stream);
+            if (cv.math == UP_MATH_F32)
+                e = up_conv2d_fwd(&cv.d, ptr(op.in), cv.w_fwd, ptr(op.out), &ep, stream);
+            else
+                e = up_conv2d_fwd_bf16(&cv.d, ptr(op.in), reinterpret_cast<const uint16_t*>(cv.w_fwd), nullptr, ptr(op.out), &ep, cv.math,
+                                       stream);
             break;
         }
         case MAXPOOL:
-            e = up_maxpool3s2_fwd(ptr(op.in), i.c, ptr(op.out), o.c, reinterpret_cast<uint8_t*>(ptr(op.res)), op.n, i.h, i.w, i.c, o.h, o.w,
-                                  stream);
+            e = up_maxpool3s2_fwd_t(ptr(op.in), i.c, ptr(op.out), o.c, reinterpret_cast<uint8_t*>(ptr(op.res)), op.n, i.h, i.w, i.c, o.h,
+                                    o.w, dt(i), dt(o), stream);
             break;
         case BILINEAR:
-            e = up_bilinear_fwd(ptr(op.in), i.c, ptr(op.out), o.c, op.n, i.h, i.w, i.c, o.h, o.w, stream);
+            e = up_bilinear_fwd_t(ptr(op.in), i.c, ptr(op.out), o.c, op.n, i.h, i.w, i.c, o.h, o.w, dt(i), stream);
             break;
         case GAP:
-            e = up_gap_fwd(ptr(op.in), i.c, ptr(op.out), op.n, i.h * i.w, i.c, stream);
+            e = up_gap_fwd_t(ptr(op.in), i.c, ptr(op.out), op.n, i.h * i.w, i.c, dt(i), stream);
             break;
-        case COPY:
-            e = up_copy2d(ptr(op.in), op.lds, ptr(op.out), op.ldd, op.rows, op.ch, stream);
+        case COPY: {      // the kernel moves 4-byte words: bf16 rows as half as many (strides, widths and offsets are multiples of 32)
+            const int per = (int)(4 / i.elem);
+            e = up_copy2d(ptr(op.in), op.lds / per, ptr(op.out), op.ldd / per, op.rows, op.ch / per, stream);
             break;
+        }
         case ZERO:
             if (hipMemsetAsync(ptr(op.out), 0, o.bytes, as_stream(stream)) != hipSuccess) e = check_launch(what);
             break;
@@ -801,8 +840,9 @@ struct Store {                 // one packed forward weight image (+ bias)
     std::string name;          // a state_dict prefix, or "lstm_0" / "lstm" for the stacked gate convolutions
     up_conv_desc d;            // descriptor of its first use (the packed image depends on K, C, Cp, R, S only)
     bool has_bias = false;
+    bool b16 = false;          // the bf16 hi plane of up_pack_weights_bf16 (a convolution on bf16 tensors), else the fp32 image
     float* w_fwd = nullptr;
-    float* bias = nullptr;
+    float* bias = nullptr;     // fp32 in either storage
     int parts = 0;             // stacked: 3 (g, i, o) or 8 (gx, ix, ox, fx, gh, ih, oh, fh), else 0
     float* stage_w = nullptr;  // stacked: the OIHW image the parts are copied into (pad channels zero)
     float* stage_b = nullptr;  // stacked: [parts][cg] the parts' biases
@@ -819,6 +859,9 @@ struct Entry {                 // one listed convolution
 struct Weights {
     std::vector<Store> stores;
     std::vector<Entry> entries;
+    uint16_t* lo = nullptr;    // bf16 storage: where up_pack_weights_bf16 puts the lo plane it always writes beside the hi plane.  No
+                               // launch of the plan reads it (only UP_MATH_BF16X3 does), so ONE buffer of the largest image serves
+                               // every store, whatever the order or the streams of the set_conv calls
 
     int store_of(const std::string& name) const {
         for (size_t s = 0; s < stores.size(); ++s)
@@ -835,12 +878,16 @@ struct Weights {
                 st.name = cv.name;
                 st.d = cv.d;
                 st.has_bias = cv.has_bias;
+                st.b16 = cv.math != UP_MATH_F32;
                 st.parts = cv.name == "lstm_0" ? 3 : cv.name == "lstm" ? 8 : 0;
                 stores.push_back(st);
             }
         bool ok = true;
+        size_t lo_elems = 0;
         for (Store& st : stores) {
-            st.w_fwd = static_cast<float*>(dev_alloc((size_t)st.d.K * st.d.R * st.d.S * st.d.Cp * sizeof(float)));
+            const size_t image = (size_t)st.d.K * st.d.R * st.d.S * st.d.Cp;
+            if (st.b16) lo_elems = std::max(lo_elems, image);
+            st.w_fwd = static_cast<float*>(dev_alloc(image * (st.b16 ? sizeof(uint16_t) : sizeof(float))));
             if (st.has_bias) st.bias = static_cast<float*>(dev_alloc((size_t)st.d.K * sizeof(float)));
             ok = ok && st.w_fwd && (!st.has_bias || st.bias);
             if (st.parts) {
@@ -848,6 +895,10 @@ struct Weights {
                 st.stage_b = static_cast<float*>(dev_alloc((size_t)st.parts * cg * sizeof(float)));
                 ok = ok && st.stage_w && st.stage_b;
             }
+        }
+        if (lo_elems) {
+            lo = static_cast<uint16_t*>(dev_alloc(lo_elems * sizeof(uint16_t)));
+            ok = ok && lo;
         }
         for (size_t f = 0; f < count; ++f)
             for (Conv& cv : progs[f].convs) {
@@ -873,6 +924,7 @@ struct Weights {
             dev_free(st.stage_w);
             dev_free(st.stage_b);
         }
+        dev_free(lo);
     }
 };
 
@@ -897,7 +949,11 @@ static int set_conv_check(const Weights* w, int i, const float* w_oihw, const fl
 static int set_conv_whole(Weights& w, int i, const float* w_oihw, const float* bias, void* stream) {
     const Entry& en = w.entries[i];
     const Store& st = w.stores[en.store];
-    if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) return e;
+    if (st.b16) {
+        if (int e = up_pack_weights_bf16(&st.d, w_oihw, reinterpret_cast<uint16_t*>(st.w_fwd), w.lo, nullptr, nullptr, stream)) return e;
+    } else if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) {
+        return e;
+    }
     if (bias)
         if (int e = up_copy2d(bias, st.d.K, st.bias, st.d.K, 1, st.d.K, stream)) return e;
     for (Entry& other : w.entries)
@@ -943,13 +999,22 @@ static const size_t IMAGE_FORMS = sizeof(plan::IMAGE_PROGRAMS) / sizeof(plan::IM
 struct up_unipose_plan {
     up_unipose_config cfg;
     Plan prog[IMAGE_FORMS];    // as IMAGE_PROGRAMS lists them
+    int dtype = UP_DT_F32;     // the storage behind the stem: activations in the workspace and the packed weight images
     plan::Weights w;           // the listed convolutions are those of program 0: the 116 of the forward, wasp.conv2 twice
     size_t ws_bytes = 0;       // the largest of the programs that count toward it, and ...
     size_t flip_ws_bytes = 0;  // ... toward the flip test's
 };
 
 extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** out) {
+    return up_unipose_plan_create_t(cfg, UP_DT_F32, out);
+}
+
+extern "C" int up_unipose_plan_dtype(const up_unipose_plan* pl) { return pl ? pl->dtype : UP_ERR_INVALID; }
+
+extern "C" int up_unipose_plan_create_t(const up_unipose_config* cfg, int dtype, up_unipose_plan** out) {
     UP_REQUIRE(cfg && out, UP_ERR_INVALID, "unipose_plan_create: null argument");
+    UP_REQUIRE(dtype == UP_DT_F32 || dtype == UP_DT_BF16, UP_ERR_INVALID, "unipose_plan_create: storage type %d (UP_DT_F32 or UP_DT_BF16)",
+               dtype);
     UP_REQUIRE(cfg->batch > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->out_channels > 0, UP_ERR_INVALID,
                "unipose_plan_create: batch %d, input %dx%d, %d output channels", cfg->batch, cfg->height, cfg->width, cfg->out_channels);
     UP_REQUIRE(cfg->output_stride == 16 || cfg->output_stride == 8, UP_ERR_UNSUPPORTED,
@@ -957,9 +1022,10 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
     up_unipose_plan* pl = new (std::nothrow) up_unipose_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
+    pl->dtype = dtype;
     for (size_t f = 0; f < IMAGE_FORMS; ++f) {
         const plan::Program& g = plan::IMAGE_PROGRAMS[f];
-        plan::build(pl->prog[f], pl->cfg, g);
+        plan::build(pl->prog[f], pl->cfg, g, dtype);
         if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
         if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
     }

@@ -23,6 +23,11 @@ to the input size, as the module does; ``keypoints`` then decodes on that grid w
 The launches are those of the drop-in module's folded forward, so the results agree bit for bit
 (tests/test_plan_emu.py, tests/test_plan_gpu.py).  Weights are captured at construction: call ``refresh(model)`` after
 changing them.  Inference only.
+
+``UniPosePlan(..., storage="bf16")`` runs every method in bf16 STORAGE: the launches of the folded module under
+``ops.set_conv_math("bf16s")`` — bf16 activations and weight images behind the fp32 stem, fp32 accumulation, fp32 maps out of the
+last convolution — again with equal bits (tests/test_plan_bf16_*.py).  Inputs, results and ``refresh`` stay fp32; the plan neither
+reads nor sets ``ops.CONV_MATH``, so plans of both storages can be alive and called in turn.
 """
 from __future__ import annotations
 
@@ -78,11 +83,15 @@ class _Plan:
     _prefix = None
     bbox = False
 
-    def _create(self, cfg, device):
+    def _create(self, cfg, device, dtype=None):
+        """dtype: None for the plan's plain create entry, else the storage type code of its `_create_t` form"""
         L = _C.lib()
         self.cfg, self.device, self.workspace = cfg, device, None
         self._plan = C.c_void_p()
-        _C.check(getattr(L, self._prefix + "_create")(C.byref(cfg), C.byref(self._plan)), self._prefix[3:] + "_create")
+        if dtype is None:
+            _C.check(getattr(L, self._prefix + "_create")(C.byref(cfg), C.byref(self._plan)), self._prefix[3:] + "_create")
+        else:
+            _C.check(getattr(L, self._prefix + "_create_t")(C.byref(cfg), dtype, C.byref(self._plan)), self._prefix[3:] + "_create_t")
         self._ws(getattr(L, self._prefix + "_workspace")(self._plan))
 
     def _stream(self):
@@ -179,10 +188,17 @@ class _Plan:
             pass
 
 
+# storage="..." of UniPosePlan -> (what plan.storage reads back, UP_DT_* code): the names ops.set_conv_math takes for the two modes
+_STORAGE = {"f32": ("f32", 0), "fp32": ("f32", 0), "bf16": ("bf16", 1), "bf16s": ("bf16", 1), "bf16_storage": ("bf16", 1)}
+
+
 class UniPosePlan(_Plan):
     _prefix = "up_unipose_plan"
 
-    def __init__(self, model, batch: int, height: int, width: int):
+    def __init__(self, model, batch: int, height: int, width: int, storage: str = "f32"):
+        if not isinstance(storage, str) or storage not in _STORAGE:
+            raise ValueError(f"UniPosePlan: storage {storage!r}; one of {sorted(_STORAGE)}")
+        self.storage, dtype = _STORAGE[storage]
         if model.training:
             raise ValueError("UniPosePlan captures the inference forward: call model.eval() first")
         if batch < 1 or height < 8 or width < 8:
@@ -195,7 +211,8 @@ class UniPosePlan(_Plan):
         self.num_classes = model.num_classes
         out_channels = model.decoder.last_conv[8].out_channels
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
-        self._create(_Config(batch, height, width, os_, out_channels), w0.device)
+        # (the default goes through up_unipose_plan_create, as before the storage option)
+        self._create(_Config(batch, height, width, os_, out_channels), w0.device, dtype if dtype else None)
         self.batch, self.height, self.width, self.out_channels = batch, height, width, out_channels
         # heat-map size: three ceil-halvings (7x7 stride-2 stem, 3x3 stride-2 max-pool, layer2's stride 2), the arithmetic of
         # plan.hip's build(): ceil(H / 8), NOT H // 8 — the two differ whenever H % 8 != 0 (a 52 x 52 input gives 7 x 7 maps)
@@ -205,7 +222,8 @@ class UniPosePlan(_Plan):
         self.refresh(model)
 
     def refresh(self, model):
-        """(re)load the weights: BatchNorm folded in float64 and rounded once, like checkpoint.fold_batchnorm / load_folded"""
+        """(re)load the weights: BatchNorm folded in float64 and rounded once, like checkpoint.fold_batchnorm / load_folded; the
+        plan packs them in its own storage type (bf16 images behind the stem in bf16 storage)"""
         _set_convs(self, "up_unipose_plan", fold_batchnorm(model))
 
     def _input(self, x):
