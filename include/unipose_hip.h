@@ -909,14 +909,29 @@ int up_unipose_frame_final_preds(up_unipose_plan* plan, const void* src_hwc, int
  * or misaligned state included); the outputs are then untouched.  Workspace: each asks for
  * up_unipose_lstm_plan_program_workspace(plan, UP_PROGRAM_FROM_FRAMES + k), k = 2, 4, 5, 6, 7, 8 naming the program it otherwise
  * equals (0 for any other k; the flip forms keep the mirrored input alive through the first pass); neither
- * up_unipose_lstm_plan_workspace() nor up_unipose_lstm_plan_flip_workspace() changes. */
+ * up_unipose_lstm_plan_workspace() nor up_unipose_lstm_plan_flip_workspace() changes.
+ * Storage: up_unipose_lstm_plan_create_t(cfg, dtype, &plan) with dtype = UP_DT_F32 (what up_unipose_lstm_plan_create makes) or
+ * UP_DT_BF16; any other dtype is UP_ERR_INVALID, *plan stays untouched and nothing is allocated.  up_unipose_lstm_plan_dtype() reads
+ * it back.  A UP_DT_BF16 plan runs every program above with the launches of the folded module under the bf16-storage arithmetic:
+ * the trunk as the image plan's (fp32 input pass and stem, bf16 tensors and weight images behind it, decoder.last_conv.8 the
+ * UP_MATH_BF16S_F32OUT launch).  Everything behind the trunk stays fp32 TENSORS, because the 15 / 16-channel state lies outside the
+ * 32-lane granularity of the bf16 kernels: the hand-over tensor of rup4(K+2) lanes (zeroed in every call, the K+1 real lanes of the
+ * trunk's 32-lane maps copied in, the pooled centre map in lane K+1), cells, hides, the gate kernels, the head and every ending.  The
+ * convolutions of those tensors pick their arithmetic by their physical input width: Cp % 32 == 0 runs
+ * up_conv2d_fwd_bf16(UP_MATH_BF16) — fp32 in and out, bf16 operands, the weight's hi plane — (conv2 .. conv5, and the stacked gate
+ * convolution where 2 * rup4(K+2) is a multiple of 32, e.g. K = 13), anything else up_conv2d_fwd (lstm_0, conv1, the gate
+ * convolution at K = 15).  The stacked gate weights are stacked in fp32 and rounded once.  Nothing changes at the boundary: the same
+ * arguments, fp32 state (up_unipose_lstm_plan_state_bytes() is equal for both storages), the same refusals; the workspace figures
+ * are the plan's own (smaller than the fp32 plan's). */
 typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
 typedef struct {
     int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */
     int32_t output_stride;                  /* 16 or 8 */
     int32_t num_classes;                    /* K: heat-maps K+1, recurrent state K+2 channels */
 } up_unipose_lstm_config;
-int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** plan);
+int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** plan);   /* = ..._create_t(cfg, UP_DT_F32, plan) */
+int up_unipose_lstm_plan_create_t(const up_unipose_lstm_config* cfg, int dtype, up_unipose_lstm_plan** plan);
+int up_unipose_lstm_plan_dtype(const up_unipose_lstm_plan* plan);      /* UP_DT_F32 / UP_DT_BF16; UP_ERR_INVALID for NULL */
 void up_unipose_lstm_plan_destroy(up_unipose_lstm_plan* plan);
 int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* plan);
 const char* up_unipose_lstm_plan_conv_name(const up_unipose_lstm_plan* plan, int i);

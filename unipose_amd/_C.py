@@ -180,6 +180,8 @@ SIGNATURES = {
     "up_clip_avgpool9s8_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "up_clip_nhwc_to_nchw": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "up_unipose_lstm_plan_create": (_i, [_p, C.POINTER(_p)]),
+    "up_unipose_lstm_plan_create_t": (_i, [_p, _i, C.POINTER(_p)]),
+    "up_unipose_lstm_plan_dtype": (_i, [_p]),
     "up_unipose_lstm_plan_destroy": (None, [_p]),
     "up_unipose_lstm_plan_num_convs": (_i, [_p]),
     "up_unipose_lstm_plan_conv_name": (C.c_char_p, [_p, _i]),

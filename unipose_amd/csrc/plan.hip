@@ -13,7 +13,9 @@
 // (tests/test_plan_*.py, tests/test_lstm_plan_*.py).  Training has no whole-graph entry: it runs through autograd.
 // The image plan also runs in bf16 STORAGE (up_unipose_plan_create_t with UP_DT_BF16): the same programs with bf16 tensors and
 // weight images behind the fp32 stem, the launches of the folded module under ops.set_conv_math("bf16s") — equal bits again
-// (tests/test_plan_bf16_*.py).  The element type is a parameter of trunk() and of the weight store; the video plan passes fp32.
+// (tests/test_plan_bf16_*.py).  The element type is a parameter of trunk() and of the weight store.  The video plan takes it too
+// (up_unipose_lstm_plan_create_t): a bf16 trunk that hands over fp32 heat-maps, the ConvLSTM state and the head fp32 tensors whose
+// convolutions of 32-aligned input width run on bf16 operands, as the module's do (tests/test_lstm_plan_bf16_*.py).
 //
 // What the file holds, top to bottom:
 //   Plan        one program: tensors, convolutions, ops, and the first-fit workspace layout over the tensors' live ranges
@@ -73,7 +75,8 @@ struct Conv {
     up_conv_desc d;
     int relu;
     bool has_bias;         // the folded network has a bias on every convolution but wasp.conv2
-    int math = UP_MATH_F32;   // UP_MATH_F32: up_conv2d_fwd; UP_MATH_BF16S / UP_MATH_BF16S_F32OUT: up_conv2d_fwd_bf16 on bf16 tensors
+    int math = UP_MATH_F32;   // UP_MATH_F32: up_conv2d_fwd; UP_MATH_BF16S / UP_MATH_BF16S_F32OUT: up_conv2d_fwd_bf16 on bf16 tensors;
+                              // UP_MATH_BF16: up_conv2d_fwd_bf16 on fp32 tensors (bf16 operands: the weight's hi plane)
     float* w_fwd = nullptr;   // the plan's store of that name (Weights::bind): the fp32 image, or the bf16 hi plane
     float* bias = nullptr;
 };
@@ -107,8 +110,10 @@ struct Plan {
     size_t ws_bytes = 0;
     // layout(): let the free block under the top grow into a tensor that fits nowhere.  The bf16 image plan sets it: its largest
     // tensor is the up-sampled fp32 maps at the end of program 1 (rup32 lanes), larger than anything the bf16 trunk leaves free.
+    // The bf16 video plan sets it too: behind the fp32 stem the bf16 tensors leave free blocks a later, larger tensor can grow from.
     // The fp32 plans keep the layout, and so the workspace figures, they always had.
     bool grow_tail = false;
+    int dt = UP_DT_F32;        // the plan's storage: what conv() picks the arithmetic of an fp32 tensor's convolution by
 
     int tensor(int n, int h, int w, int c, size_t elem = 4) {
         Tensor t;
@@ -135,7 +140,9 @@ struct Plan {
     // conv (+ folded-BatchNorm bias) (+ residual) (+ ReLU) of `images` images at (h, w) with cp physical input channels.  The
     // kernels follow the tensor's type (ops.conv_fwd_raw): a bf16 input runs up_conv2d_fwd_bf16 in bf16 storage and the output is
     // padded to a multiple of 32 channels (ops.make_desc); f32out: the network's last convolution, bf16 in, fp32 out.  A padded
-    // output the plan makes itself is zeroed first, as the module allocates it: the launch writes lanes [0, K) only.
+    // output the plan makes itself is zeroed first, as the module allocates it: the launch writes lanes [0, K) only.  An fp32
+    // tensor in a bf16 plan with cp % 32 == 0 runs up_conv2d_fwd_bf16 too, with UP_MATH_BF16: fp32 in and out (rup4 lanes), the
+    // operands rounded to bf16, the weight's hi plane only; any other fp32 tensor up_conv2d_fwd.
     Ref conv(const std::string& name, Ref x, int images, int h, int w, int cp, int c, int k, int r, int stride, int pad, int dil,
              int relu, bool has_bias, Ref res = Ref(), Ref out = Ref(), bool f32out = false) {
         const bool b16 = tensors[x.id].elem == 2;
@@ -151,7 +158,8 @@ struct Plan {
         d.Q = (w + 2 * pad - dil * (r - 1) - 1) / stride + 1;
         d.Kp = b16 ? rup32(k) : rup4(k);
         d.ldy = d.Kp;
-        cv.math = !b16 ? UP_MATH_F32 : f32out ? UP_MATH_BF16S_F32OUT : UP_MATH_BF16S;
+        if (b16) cv.math = f32out ? UP_MATH_BF16S_F32OUT : UP_MATH_BF16S;
+        else cv.math = dt == UP_DT_BF16 && cp % 32 == 0 ? UP_MATH_BF16 : UP_MATH_F32;
         if (out.id < 0) {
             out.id = tensor(images, d.P, d.Q, d.ldy, b16 && !f32out ? 2 : 4);
             if (b16 && d.ldy != k) zero(out);
@@ -266,7 +274,8 @@ static Ref bottleneck(Plan& p, const std::string& name, Ref x, int n, int& h, in
 // dt: the storage behind the stem (UP_DT_F32 / UP_DT_BF16).  In bf16 storage the launches are those of the folded module under
 // ops.set_conv_math("bf16s"): the stem stays fp32 (4 input channels: no multiple of 32), its max-pool writes bf16
 // (modules.ResNet.forward), every tensor behind it is bf16 with convolution outputs padded to 32 channels, and the last
-// convolution writes fp32 maps of rup32(out_channels) channels (modules.Decoder.forward, out_f32).  The video plan passes fp32.
+// convolution writes fp32 maps of rup32(out_channels) channels (modules.Decoder.forward, out_f32): a tensor of its own, zeroed, in
+// the video plan too, whose hand-over tensor lstm_pass() then makes.
 static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int out_channels, bool video, int dt) {
     const size_t elem = dt == UP_DT_BF16 ? 2 : 4;
     int strides[4], dils[4];
@@ -348,7 +357,7 @@ static Ref trunk(Plan& p, Ref x, int n, int& h, int& w, int output_stride, int o
     x = p.conv("decoder.last_conv.0", cat2, n, dh, dw, 320, 304, 256, 3, 1, 1, 1, 1, true);
     x = p.conv("decoder.last_conv.4", x, n, dh, dw, 256, 256, 256, 3, 1, 1, 1, 1, true);
     Ref heat;
-    if (video && rup4(out_channels) != out_channels) {
+    if (video && dt != UP_DT_BF16 && rup4(out_channels) != out_channels) {
         heat.id = p.tensor(n, dh, dw, rup4(out_channels));
         p.zero(heat);
     }
@@ -441,6 +450,7 @@ static void build(Plan& p, const up_unipose_config& c, const Program& g, int dt)
     int h = c.height, w = c.width;
     const bool frames = g.input == IN_FRAMES;
     p.grow_tail = dt == UP_DT_BF16;
+    p.dt = dt;
     // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC); from frames: the crop writes NHWC itself, and the mirror beside it
     Ref x, m;
     x.id = p.tensor(n, h, w, 4);
@@ -494,7 +504,9 @@ struct LstmPass {
 // recurrence frame by frame on rows of frame-major state tensors, the head once on the T * B hidden states.  Stacked gate
 // convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).  mirrored: the pass of the flip test.
 // mirror: from frames, the mirrored input the first pass's crop launch fills for the second.
-static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored, Ref& mirror) {
+// dt: the trunk's storage.  Everything else stays fp32 tensors in a bf16 plan, as in the module (uniposeLSTM.py:166-168): the
+// input pass, the hand-over, the state, the gate kernels and the head; Plan::conv picks each convolution's arithmetic.
+static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored, Ref& mirror, int dt) {
     const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
     const bool frames = g.input == IN_FRAMES || g.input == IN_CLIP_FRAMES;
     const int B = c.batch, T = clip ? c.frames : 1, n = T * B;
@@ -514,14 +526,16 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
         op.n = B; op.frames = T; op.ch = 3;
         p.push(op);
     }
-    Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true, UP_DT_F32);
+    Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true, dt);
     // _AddCenter: the pooled centre map in the heat-maps' spare pad channel; (K + 1) % 4 == 0: a hand-over tensor of rup4(K + 2)
-    // channels, zeros, the heat-maps copied in
+    // channels, zeros, the heat-maps copied in.  bf16 storage: the trunk's fp32 maps have rup32(K + 1) lanes, which the module slices
+    // back to the fp32 layout (uniposeLSTM.py:119-124) — always the hand-over tensor, zeroed in every call (the gate convolution
+    // reads all its lanes), the K + 1 real lanes copied in
     Ref z = heat;
-    if (rup4(hc) == hc) {
+    if (dt == UP_DT_BF16 || rup4(hc) == hc) {
         z.id = p.tensor(n, h, w, ldo);
         p.zero(z);
-        p.copy(heat, hc, z, ldo, 0, (int64_t)n * h * w, hc);
+        p.copy(heat, p.tensors[heat.id].c, z, ldo, 0, (int64_t)n * h * w, hc);
     }
     const int ldz = p.tensors[z.id].c;       // == ldo either way
     {
@@ -602,15 +616,18 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
     return r;
 }
 
-static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g) {
+static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g, int dt) {
     const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
     const int B = c.batch, T = clip ? c.frames : 1;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
     Ref mirror;
-    const LstmPass a = lstm_pass(p, c, g, false, mirror);
+    p.dt = dt;
+    p.grow_tail = dt == UP_DT_BF16;      // measured on the figures: every program of a bf16 plan needs less with it (B = 8, T = 5, 368 x 368:
+                                         // 520 MB against 607 MB; the fp32 plan 1148 MB), so it is set; fp32 plans keep their layout
+    const LstmPass a = lstm_pass(p, c, g, false, mirror, dt);
     Op op;
     if (g.flip) {
-        const LstmPass m = lstm_pass(p, c, g, true, mirror);
+        const LstmPass m = lstm_pass(p, c, g, true, mirror, dt);
         op.kind = MERGE;                       // in place (NHWC): out == a with equal strides; both passes are frame-major
         op.in = a.y; op.aux = m.y; op.out = a.y;
         op.n = T * B; op.ch = hc;
@@ -840,7 +857,8 @@ struct Store {                 // one packed forward weight image (+ bias)
     std::string name;          // a state_dict prefix, or "lstm_0" / "lstm" for the stacked gate convolutions
     up_conv_desc d;            // descriptor of its first use (the packed image depends on K, C, Cp, R, S only)
     bool has_bias = false;
-    bool b16 = false;          // the bf16 hi plane of up_pack_weights_bf16 (a convolution on bf16 tensors), else the fp32 image
+    bool b16 = false;          // the bf16 hi plane of up_pack_weights_bf16 (a launch of up_conv2d_fwd_bf16, whatever its tensors' type),
+                               // else the fp32 image
     float* w_fwd = nullptr;
     float* bias = nullptr;     // fp32 in either storage
     int parts = 0;             // stacked: 3 (g, i, o) or 8 (gx, ix, ox, fx, gh, ih, oh, fh), else 0
@@ -945,15 +963,16 @@ static int set_conv_check(const Weights* w, int i, const float* w_oihw, const fl
                en.has_bias ? "needs" : "has no");
     return UP_OK;
 }
+// an OIHW image into its store, in the store's type (a stacked one: stacked in fp32 first, rounded once, like ops._packed_bf16)
+static int pack(const Weights& w, const Store& st, const float* w_oihw, void* stream) {
+    if (st.b16) return up_pack_weights_bf16(&st.d, w_oihw, reinterpret_cast<uint16_t*>(st.w_fwd), w.lo, nullptr, nullptr, stream);
+    return up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream);
+}
 // an entry that is a whole parameter: packed into its store; every listing of the name is set with it
 static int set_conv_whole(Weights& w, int i, const float* w_oihw, const float* bias, void* stream) {
     const Entry& en = w.entries[i];
     const Store& st = w.stores[en.store];
-    if (st.b16) {
-        if (int e = up_pack_weights_bf16(&st.d, w_oihw, reinterpret_cast<uint16_t*>(st.w_fwd), w.lo, nullptr, nullptr, stream)) return e;
-    } else if (int e = up_pack_weights(&st.d, w_oihw, st.w_fwd, nullptr, stream)) {
-        return e;
-    }
+    if (int e = pack(w, st, w_oihw, stream)) return e;
     if (bias)
         if (int e = up_copy2d(bias, st.d.K, st.bias, st.d.K, 1, st.d.K, stream)) return e;
     for (Entry& other : w.entries)
@@ -1230,6 +1249,7 @@ static const size_t LSTM_FORMS = sizeof(plan::LSTM_PROGRAMS) / sizeof(plan::LSTM
 struct up_unipose_lstm_plan {
     up_unipose_lstm_config cfg;
     Plan prog[LSTM_FORMS];     // as LSTM_PROGRAMS lists them
+    int dtype = UP_DT_F32;     // the trunk's storage: its activations and packed weight images; state, head and all I/O are fp32
     plan::Weights w;
     size_t ws_bytes = 0;       // the largest of the programs without the flip test
     size_t flip_ws_bytes = 0;  // the largest of those with it
@@ -1237,7 +1257,15 @@ struct up_unipose_lstm_plan {
 };
 
 extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** out) {
+    return up_unipose_lstm_plan_create_t(cfg, UP_DT_F32, out);
+}
+
+extern "C" int up_unipose_lstm_plan_dtype(const up_unipose_lstm_plan* pl) { return pl ? pl->dtype : UP_ERR_INVALID; }
+
+extern "C" int up_unipose_lstm_plan_create_t(const up_unipose_lstm_config* cfg, int dtype, up_unipose_lstm_plan** out) {
     UP_REQUIRE(cfg && out, UP_ERR_INVALID, "unipose_lstm_plan_create: null argument");
+    UP_REQUIRE(dtype == UP_DT_F32 || dtype == UP_DT_BF16, UP_ERR_INVALID,
+               "unipose_lstm_plan_create: storage type %d (UP_DT_F32 or UP_DT_BF16)", dtype);
     UP_REQUIRE(cfg->batch > 0 && cfg->frames > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->num_classes > 0, UP_ERR_INVALID,
                "unipose_lstm_plan_create: batch %d, %d frames, input %dx%d, %d classes", cfg->batch, cfg->frames, cfg->height,
                cfg->width, cfg->num_classes);
@@ -1253,9 +1281,10 @@ extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up
     up_unipose_lstm_plan* pl = new (std::nothrow) up_unipose_lstm_plan();
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_lstm_plan_create: out of host memory");
     pl->cfg = *cfg;
+    pl->dtype = dtype;
     for (size_t f = 0; f < LSTM_FORMS; ++f) {
         const plan::Program& g = plan::LSTM_PROGRAMS[f];
-        plan::build_lstm(pl->prog[f], pl->cfg, g);
+        plan::build_lstm(pl->prog[f], pl->cfg, g, dtype);
         if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
         if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
         for (const plan::Op& op : pl->prog[f].ops)       // the hidden state STATE_OUT copies: its tensor's padded size
@@ -1324,7 +1353,7 @@ extern "C" int up_unipose_lstm_plan_set_conv(up_unipose_lstm_plan* pl, int i, co
     int e = st.parts == 3 ? up_copy2d(st.stage_b, 3 * cg, st.bias, 3 * cg, 1, 3 * cg, stream)
                           : up_add2d(st.stage_b, cg, st.stage_b + 4 * cg, cg, st.bias, cg, 4, cg, stream);
     if (e) return e;
-    return up_pack_weights(&st.d, st.stage_w, st.w_fwd, nullptr, stream);
+    return plan::pack(pl->w, st, st.stage_w, stream);
 }
 
 extern "C" size_t up_unipose_lstm_plan_workspace(const up_unipose_lstm_plan* pl) { return pl ? pl->ws_bytes : 0; }

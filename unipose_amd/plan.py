@@ -392,10 +392,18 @@ class UniPoseLSTMPlan(_Plan):
     The state is the caller's, NCHW (B, K+2, h, w) as the reference's signature has it; the (K+2, h, w) zeros of the reference's
     first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
     module ignores them at iter == 0).  Weights are captured at construction: ``refresh(model)`` after changing them.  Inference only.
+
+    ``UniPoseLSTMPlan(..., storage="bf16")`` runs every method with the launches of the folded module under
+    ``ops.set_conv_math("bf16s")`` (unipose_amd/uniposeLSTM.py): a bf16 trunk that hands over fp32 heat-maps, fp32 ConvLSTM state
+    and head, their convolutions of 32-aligned input width on bf16 operands — equal bits again (tests/test_lstm_plan_bf16_*.py).
+    Frames, centre maps, states, results and ``refresh`` stay float32; a ``stream_state()`` buffer has the same size in both storages.
     """
     _prefix = "up_unipose_lstm_plan"
 
-    def __init__(self, model, batch: int, height: int, width: int, frames: int = 1):
+    def __init__(self, model, batch: int, height: int, width: int, frames: int = 1, storage: str = "f32"):
+        if not isinstance(storage, str) or storage not in _STORAGE:
+            raise ValueError(f"UniPoseLSTMPlan: storage {storage!r}; one of {sorted(_STORAGE)}")
+        self.storage, dtype = _STORAGE[storage]
         if model.training:
             raise ValueError("UniPoseLSTMPlan captures the inference forward: call model.eval() first")
         # model.stride is not looked at: the reference's video model stores it (model/uniposeLSTM.py:71) and never up-samples, and
@@ -407,7 +415,8 @@ class UniPoseLSTMPlan(_Plan):
             raise _C.UniPoseHipError("UniPoseLSTMPlan needs a CUDA(HIP) model; there is no CPU fallback")
         self.num_classes = K = model.num_classes
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
-        self._create(_LstmConfig(batch, frames, height, width, os_, K), w0.device)
+        # (the default goes through up_unipose_lstm_plan_create, as before the storage option)
+        self._create(_LstmConfig(batch, frames, height, width, os_, K), w0.device, dtype if dtype else None)
         self.batch, self.frames, self.height, self.width = batch, frames, height, width
         self.out_channels, self.out_height, self.out_width = K + 1, (height - 1) // 8 + 1, (width - 1) // 8 + 1
         self.refresh(model)
