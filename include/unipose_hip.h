@@ -440,6 +440,24 @@ int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C,
 int up_clip_nchw_to_nhwc_flip(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream);
 int up_clip_avgpool9s8_flip_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q, void* stream);
 /* (up_clip_heatmap_decode / up_clip_final_preds are declared with their neighbours below) */
+/* The _strided forms of the clip kernels that write frame-major images (ABI 10 additions; the one-pass flip test of the video plan
+ * below; up_clip_crop_to_nhwc_strided, up_clip_center_pool_strided and up_clip_center_pool_flip_strided are declared with their
+ * neighbours).  Each is its neighbour with two more arguments: the output is frames of frame_images >= B images, and the image
+ * written for sample (b, t) is t * frame_images + first + b instead of t * B + b; images a launch does not address, and the lanes the
+ * neighbour leaves alone, are not touched.  frame_images = B, first = 0 is the neighbour itself (which keeps its own launch); two
+ * launches with frame_images = 2 B, first = 0 and first = B fill the two halves of every frame of one tensor.  One device function
+ * per pair, so the bits of an image are the neighbour's.  The crop's y_nhwc and y_flip_nhwc keep separate pointers and share
+ * frame_images / first: one launch, the source read once.
+ * UP_ERR_INVALID (nothing launched): first < 0, frame_images < first + B, T * frame_images beyond the int32 range, and what the
+ * neighbour refuses (up_clip_avgpool9s8_fwd_strided: what up_clip_avgpool9s8_flip_fwd refuses). */
+int up_clip_nchw_to_nhwc_strided(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, int frame_images, int first,
+                                 void* stream);
+int up_clip_nchw_to_nhwc_flip_strided(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, int frame_images, int first,
+                                      void* stream);
+int up_clip_avgpool9s8_fwd_strided(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                                   int frame_images, int first, void* stream);
+int up_clip_avgpool9s8_flip_fwd_strided(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                                        int frame_images, int first, void* stream);
 /* nn.Dropout (wasp.py:63, decoder.py:25,29): keep-mask from a counter hash of (seed, element index)
  * or, when ext_mask != NULL, from the caller (float 0/1) — the injectable-RNG hook used for parity.
  * UP_ERR_INVALID (nothing written): a null x / y / mask, n <= 0, p < 0 or p >= 1, an unknown dtype. */
@@ -546,6 +564,17 @@ int up_nchw_to_nhwc_flip(const float* x, float* y, int N, int C, int H, int W, i
 int up_flip_merge(const float* a, const float* f, int64_t in_stride_b, int64_t in_stride_j, int64_t in_stride_p, int B, int J,
                   int H, int W, const int32_t* perm_host, float* out, int64_t out_stride_b, int64_t out_stride_j,
                   int64_t out_stride_p, void* stream);
+/* up_clip_flip_merge (ABI 10 addition): up_flip_merge over T * B images behind a two-level batch index.  Image (t, b) of a and of f
+ * (its own pointer, the same strides) is read at t * in_stride_t + b * in_stride_b, out is written at t * out_stride_t + b *
+ * out_stride_b; the arithmetic (one add, one multiply by 0.5, each rounded once), the perm rule, the NaN / inf behaviour and the
+ * device function are up_flip_merge's.  With in_stride_t = 2 B * image, in_stride_b = image, f = a + B * image it merges the two
+ * halves of every frame of a (T * 2 B) tensor into a compact frame-major (T * B) one in one launch; with in_stride_t = B *
+ * in_stride_b and out_stride_t = B * out_stride_b it is up_flip_merge of T * B images.
+ * UP_ERR_INVALID / UP_ERR_UNSUPPORTED (nothing launched): as up_flip_merge, with T and the two frame strides among the sizes and
+ * strides, and the offset of the last element of the last frame within int32. */
+int up_clip_flip_merge(const float* a, const float* f, int64_t in_stride_t, int64_t in_stride_b, int64_t in_stride_j,
+                       int64_t in_stride_p, int B, int T, int J, int H, int W, const int32_t* perm_host, float* out, int64_t out_stride_t,
+                       int64_t out_stride_b, int64_t out_stride_j, int64_t out_stride_p, void* stream);
 int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W, int res0,
                    int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals, void* stream);
 int up_clip_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int T, int J, int H, int W,
@@ -656,6 +685,10 @@ int up_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, in
 int up_clip_crop_to_nhwc(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
                          const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv, float* y_nhwc,
                          float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream);
+/* ... into frames of frame_images images (the _strided forms above): image t * frame_images + first + b of y_nhwc and of y_flip_nhwc */
+int up_clip_crop_to_nhwc_strided(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                 const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv,
+                                 float* y_nhwc, float* y_flip_nhwc, int Ho, int Wo, int ldy, int frame_images, int first, void* stream);
 
 /* ---- the pooled centre map straight from the centre (ABI 10 additions) ----
  * What the video network does with a centre map is AvgPool2d(9,8,1) down to the heat-maps' grid (uniposeLSTM.py:75,114): these
@@ -679,6 +712,11 @@ int up_clip_center_pool(const double* center_xy, double sigma, float* y, int ldy
                         void* stream);
 int up_clip_center_pool_flip(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
                              void* stream);
+/* ... into frames of frame_images images (the _strided forms above): channel coff of image t * frame_images + first + b */
+int up_clip_center_pool_strided(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P,
+                                int Q, int frame_images, int first, void* stream);
+int up_clip_center_pool_flip_strided(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W, int P,
+                                     int Q, int frame_images, int first, void* stream);
 
 /* ---- PCK / PCKh evaluation (utils/evaluate.py:5-29 calc_dists / dist_acc, :58-172 accuracy) ----
  * From the joint coordinates of the predicted and the target heat-maps (two up_heatmap_argmax calls), entirely on
@@ -797,8 +835,19 @@ int up_persons_decode(const float* maps, int64_t stride_b, int64_t stride_j, int
  * passes are the `_t` forms, and decoder.last_conv.8 is the UP_MATH_BF16S_F32OUT launch: the endings read fp32 NHWC maps of
  * out_channels rounded up to 32 lanes.  The plan keeps bf16 weight images (the hi plane of up_pack_weights_bf16; fp32 for the
  * stem) and fp32 biases.  Nothing changes at the boundary: fp32 input or source frames, fp32 results, folded fp32 OIHW weights
- * through up_unipose_plan_set_conv, the same refusals.  The workspace figures are the plan's own (smaller than the fp32 plan's). */
+ * through up_unipose_plan_set_conv, the same refusals.  The workspace figures are the plan's own (smaller than the fp32 plan's).
+ * The flip test in ONE pass: up_unipose_plan_create_ex(cfg, dtype, flags, &plan) with flags = 0 (what _create_t makes) or
+ * UP_PLAN_FLIP_ONE_PASS; any other bit is UP_ERR_INVALID, *plan stays untouched and nothing is allocated.  up_unipose_plan_flags()
+ * reads it back.  A flagged plan builds the programs with the flip test (4, 5, UP_PROGRAM_FROM_FRAMES + 4 and + 5) as one trunk
+ * over 2 * batch images, images 0 .. batch-1 the input and batch .. 2 batch-1 the mirrored input, the two layout passes (or the one
+ * crop launch) writing the halves of one tensor, and up_flip_merge reading the halves of the trunk's output.  The entries, their
+ * arguments and refusals are the same.  Its results equal, bit for bit, up_flip_merge of the two halves of up_unipose_forward of a
+ * plan of batch 2 * batch on cat(x, mirror(x)) — NOT the two-pass form's, wherever a convolution picks its kernel by the number of
+ * rows.  up_unipose_plan_flip_workspace() and up_unipose_plan_program_workspace(plan, k) report those programs' own need, about that
+ * of a forward at batch 2 * batch (the from-frames forms keep no extra tensor); every other program, up_unipose_plan_workspace()
+ * and the weights are what they are without the flag. */
 enum { UP_PROGRAM_FROM_FRAMES = 256 };
+enum { UP_PLAN_FLIP_ONE_PASS = 1 };     /* flags of up_unipose_plan_create_ex / up_unipose_lstm_plan_create_ex */
 typedef struct up_unipose_plan up_unipose_plan;
 typedef struct {
     int32_t batch, height, width;   /* input (batch, 3, height, width) */
@@ -808,6 +857,8 @@ typedef struct {
 int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_plan** plan);     /* = ..._create_t(cfg, UP_DT_F32, plan) */
 int up_unipose_plan_create_t(const up_unipose_config* cfg, int dtype, up_unipose_plan** plan);
 int up_unipose_plan_dtype(const up_unipose_plan* plan);      /* UP_DT_F32 / UP_DT_BF16; UP_ERR_INVALID for NULL */
+int up_unipose_plan_create_ex(const up_unipose_config* cfg, int dtype, int flags, up_unipose_plan** plan);   /* _create_t: flags = 0 */
+int up_unipose_plan_flags(const up_unipose_plan* plan);      /* 0 / UP_PLAN_FLIP_ONE_PASS; UP_ERR_INVALID for NULL */
 void up_unipose_plan_destroy(up_unipose_plan* plan);
 int up_unipose_plan_num_convs(const up_unipose_plan* plan);
 const char* up_unipose_plan_conv_name(const up_unipose_plan* plan, int i);
@@ -922,7 +973,18 @@ int up_unipose_frame_final_preds(up_unipose_plan* plan, const void* src_hwc, int
  * convolution where 2 * rup4(K+2) is a multiple of 32, e.g. K = 13), anything else up_conv2d_fwd (lstm_0, conv1, the gate
  * convolution at K = 15).  The stacked gate weights are stacked in fp32 and rounded once.  Nothing changes at the boundary: the same
  * arguments, fp32 state (up_unipose_lstm_plan_state_bytes() is equal for both storages), the same refusals; the workspace figures
- * are the plan's own (smaller than the fp32 plan's). */
+ * are the plan's own (smaller than the fp32 plan's).
+ * The flip test in ONE pass: up_unipose_lstm_plan_create_ex(cfg, dtype, flags, &plan) with flags = 0 (what _create_t makes) or
+ * UP_PLAN_FLIP_ONE_PASS; any other bit is UP_ERR_INVALID, *plan stays untouched and nothing is allocated.
+ * up_unipose_lstm_plan_flags() reads it back.  A flagged plan builds programs 4, 5, UP_PROGRAM_FROM_FRAMES + 4 and + 5 as ONE pass over
+ * frames of 2 B images: frame-major image t * 2 B + b is the plain sample, t * 2 B + B + b its mirror (the _strided layout, pooling,
+ * crop and centre-pool entries write the halves), the gate convolution of frame t runs on 2 B contiguous rows, so each half keeps its
+ * own state, the head runs once on T * 2 B hidden states, and up_clip_flip_merge merges the halves of conv5's output into a compact
+ * frame-major tensor the endings read as before.  Entries, arguments and refusals are the same (no state is returned).  The results
+ * equal, bit for bit, up_flip_merge, frame by frame, of the two batch halves of up_unipose_lstm_clip of a plan of batch 2 B on
+ * cat(x, mirror(x)), cat(center, mirror(center)) — not the two-pass form's wherever a convolution picks its kernel by the number of
+ * rows.  up_unipose_lstm_plan_flip_workspace() and ..._program_workspace(plan, k) report those programs' own need (about a clip at
+ * batch 2 B); every other program, up_unipose_lstm_plan_workspace() and up_unipose_lstm_plan_state_bytes() are unchanged. */
 typedef struct up_unipose_lstm_plan up_unipose_lstm_plan;
 typedef struct {
     int32_t batch, frames, height, width;   /* clip (batch, frames, 3, height, width); frames = 1 if only the step form is used */
@@ -932,6 +994,8 @@ typedef struct {
 int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up_unipose_lstm_plan** plan);   /* = ..._create_t(cfg, UP_DT_F32, plan) */
 int up_unipose_lstm_plan_create_t(const up_unipose_lstm_config* cfg, int dtype, up_unipose_lstm_plan** plan);
 int up_unipose_lstm_plan_dtype(const up_unipose_lstm_plan* plan);      /* UP_DT_F32 / UP_DT_BF16; UP_ERR_INVALID for NULL */
+int up_unipose_lstm_plan_create_ex(const up_unipose_lstm_config* cfg, int dtype, int flags, up_unipose_lstm_plan** plan);
+int up_unipose_lstm_plan_flags(const up_unipose_lstm_plan* plan);      /* 0 / UP_PLAN_FLIP_ONE_PASS; UP_ERR_INVALID for NULL */
 void up_unipose_lstm_plan_destroy(up_unipose_lstm_plan* plan);
 int up_unipose_lstm_plan_num_convs(const up_unipose_lstm_plan* plan);
 const char* up_unipose_lstm_plan_conv_name(const up_unipose_lstm_plan* plan, int i);

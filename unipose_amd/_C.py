@@ -211,6 +211,18 @@ SIGNATURES = {
                                                     _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "up_unipose_lstm_stream_frame_final_preds": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, _p, C.c_double, _p, _i, _p, _i, _i,
                                                       _p, _p, _p, _p, _p, _sz, _p]),
+    "up_clip_nchw_to_nhwc_strided": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_nchw_to_nhwc_flip_strided": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_avgpool9s8_fwd_strided": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_avgpool9s8_flip_fwd_strided": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_crop_to_nhwc_strided": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _f, _f, _f, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "up_clip_center_pool_strided": (_i, [_p, C.c_double, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_center_pool_flip_strided": (_i, [_p, C.c_double, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "up_clip_flip_merge": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _p, _i64, _i64, _i64, _i64, _p]),
+    "up_unipose_plan_create_ex": (_i, [_p, _i, _i, C.POINTER(_p)]),
+    "up_unipose_plan_flags": (_i, [_p]),
+    "up_unipose_lstm_plan_create_ex": (_i, [_p, _i, _i, C.POINTER(_p)]),
+    "up_unipose_lstm_plan_flags": (_i, [_p]),
     "up_profile_variants": (_i, []),
     "up_profile_variant_name": (C.c_char_p, [_i]),
     "up_profile_begin": (_i, []),
@@ -222,6 +234,7 @@ SIGNATURES = {
 # UP_PROGRAM_FROM_FRAMES: up_unipose_plan_program_workspace(plan, 256 + k), k = 0, 4, 5, 6;
 # up_unipose_lstm_plan_program_workspace(plan, 256 + k), k = 2, 4, 5, 6, 7, 8
 PROGRAM_FROM_FRAMES = 256
+PLAN_FLIP_ONE_PASS = 1          # UP_PLAN_FLIP_ONE_PASS: flags of up_unipose_plan_create_ex / up_unipose_lstm_plan_create_ex
 
 _lib = None
 # Set ONLY by tests/conftest.py when it points the binding at the CPU emulation build of the same

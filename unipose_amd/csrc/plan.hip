@@ -84,7 +84,7 @@ struct Conv {
 enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW, DECODE, PERSONS, TO_NHWC_FLIP, MERGE, FINAL, CROP,
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL, CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL,
-    STATE_IN, STATE_OUT, CLIP_CROP, CENTER_POOL, CLIP_CENTER_POOL, CLIP_CENTER_POOL_FLIP
+    STATE_IN, STATE_OUT, CLIP_CROP, CENTER_POOL, CLIP_CENTER_POOL, CLIP_CENTER_POOL_FLIP, CLIP_MERGE
 };
 enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
 // Sizes, strides and physical channel counts come from the tensors an op names; the fields below are what they do not hold.
@@ -95,6 +95,8 @@ struct Op {
     Ext ext = X;               // the layout passes and MERGE: the caller's tensor
     int n = 0;                 // images the launch works on: the batch B, or T * B in the clip's trunk and head
     int frames = 1;            // the clip kinds: T
+    int fi = 0;                // the clip kinds that write frame-major images, in a one-pass flip row: images per frame (2 B) of the
+                               // tensor written, through the kernel's _strided entry; 0: the plain entry
     int ch = 0;                // logical channels the launch reads or writes (<= the tensors' physical ones)
     int coff = 0;              // the pooling kinds: the channel of `out` the pooled centre map goes to
     int src_h = 0, src_w = 0;  // the pooling kinds: size of the caller's centre maps
@@ -382,7 +384,8 @@ enum State { STATE_NONE, STATE_NCHW, STATE_BUFFER };      // the recurrent state
 struct Program {
     int number;        // as up_*_plan_program_workspace() takes it
     Input input;
-    bool flip;         // the flip test: the network on the input and on its mirror over the same activations, then up_flip_merge
+    bool flip;         // the flip test: the network on the input and on its mirror over the same activations, then up_flip_merge;
+                       // in a plan created with UP_PLAN_FLIP_ONE_PASS these rows run ONE pass over 2 B images instead
     Ending end;
     Counts counts;
     State from = STATE_NONE, to = STATE_NONE;     // the video plan: where the state of the frame before comes from (none: LSTM_0)
@@ -393,6 +396,8 @@ struct Program {
 // through the second.  From frames ONE up_crop_to_nhwc launch stands in place of the layout pass(es): it fills the trunk's input
 // and, in the flip programs, the mirrored input too, which then stays alive through the first trunk — so those need more than
 // flip_workspace() and report their need per program only.  All but UPSAMPLED and DECODE work on the heat-maps' own grid.
+// With UP_PLAN_FLIP_ONE_PASS the rows with flip == true are built by build_one_pass() (their need: a forward at batch 2 B, with or
+// without frames); every other row is built as ever.
 static const Program IMAGE_PROGRAMS[] = {
     {0, IN_NCHW, false, END_HEAT, COUNTS_PLAIN},        // up_unipose_forward; its convolutions are the listed ones
     {1, IN_NCHW, false, END_UPSAMPLED, COUNTS_PLAIN},   // up_unipose_forward_upsampled
@@ -445,12 +450,59 @@ static size_t program_workspace(const Program (&table)[N], const Plan* prog, int
     return 0;
 }
 
-static void build(Plan& p, const up_unipose_config& c, const Program& g, int dt) {
+// The flip rows of a plan created with UP_PLAN_FLIP_ONE_PASS: ONE trunk over 2 B images, image b the input and image B + b its
+// mirror, both halves of one tensor (a Ref's `elems` reaches the second half: in the tensor's OWN elements, and the last convolution
+// of a bf16 plan writes fp32 maps of rup32 lanes).  The layout passes are the two-pass form's, the crop's one launch fills both
+// halves; the merge reads the two halves of the trunk's output.  The oracle is a plan of batch 2 B on cat(x, mirror(x)), whose
+// launches these are; not bit-equal to the two-pass form wherever a convolution picks its kernel by the row count.
+static void build_one_pass(Plan& p, const up_unipose_config& c, const Program& g, int dt) {
+    const int n = c.batch;
+    int h = c.height, w = c.width;
+    const bool frames = g.input == IN_FRAMES;
+    Ref x, m;
+    x.id = p.tensor(2 * n, h, w, 4);
+    m = x;
+    m.elems = (size_t)n * h * w * 4;
+    Op op;
+    op.kind = frames ? CROP : TO_NHWC;
+    op.out = x;
+    if (frames) op.aux = m;
+    op.ext = X;
+    op.n = n; op.ch = 3;
+    p.push(op);
+    if (!frames) {
+        op.kind = TO_NHWC_FLIP;
+        op.out = m;
+        p.push(op);
+    }
+    x = trunk(p, x, 2 * n, h, w, c.output_stride, c.out_channels, false, dt);
+    m = x;
+    m.elems = (size_t)n * h * w * p.tensors[x.id].c;
+    op = Op();
+    op.kind = MERGE;                             // into the caller's NCHW tensor, or in place on the first half
+    op.in = x; op.aux = m;
+    if (g.end == END_FINAL) op.out = x;
+    op.ext = HEAT;
+    op.n = n; op.ch = c.out_channels;
+    p.push(op);
+    if (g.end == END_FINAL) {
+        op = Op();
+        op.kind = FINAL;
+        op.in = x;
+        op.ext = HEAT;
+        op.n = n; op.ch = c.out_channels;
+        p.push(op);
+    }
+    p.layout();
+}
+
+static void build(Plan& p, const up_unipose_config& c, const Program& g, int dt, bool one_pass) {
     const int n = c.batch;
     int h = c.height, w = c.width;
     const bool frames = g.input == IN_FRAMES;
     p.grow_tail = dt == UP_DT_BF16;
     p.dt = dt;
+    if (g.flip && one_pass) return build_one_pass(p, c, g, dt);
     // input NCHW -> NHWC, 3 -> 4 channels (ops.ToNHWC); from frames: the crop writes NHWC itself, and the mirror beside it
     Ref x, m;
     x.id = p.tensor(n, h, w, 4);
@@ -504,12 +556,18 @@ struct LstmPass {
 // recurrence frame by frame on rows of frame-major state tensors, the head once on the T * B hidden states.  Stacked gate
 // convolutions are named "lstm_0" / "lstm" (the plan builds their weights from the parts).  mirrored: the pass of the flip test.
 // mirror: from frames, the mirrored input the first pass's crop launch fills for the second.
+// one_pass (the flip rows of a plan created with UP_PLAN_FLIP_ONE_PASS): the ONE pass of the flip test over frames of 2 B images,
+// image t * 2 B + b the plain sample and image t * 2 B + B + b its mirror.  The layout and pooling launches are the two passes' own
+// through their _strided entries, each writing its half of every frame (the crop's one launch both); everything behind them is the
+// plain pass at batch 2 B: the gate convolution of frame t runs on 2 B contiguous rows, so each half keeps its own state.
 // dt: the trunk's storage.  Everything else stays fp32 tensors in a bf16 plan, as in the module (uniposeLSTM.py:166-168): the
 // input pass, the hand-over, the state, the gate kernels and the head; Plan::conv picks each convolution's arithmetic.
-static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored, Ref& mirror, int dt) {
+static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Program& g, bool mirrored, Ref& mirror, int dt,
+                          bool one_pass = false) {
     const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
     const bool frames = g.input == IN_FRAMES || g.input == IN_CLIP_FRAMES;
-    const int B = c.batch, T = clip ? c.frames : 1, n = T * B;
+    const int S = c.batch;                       // samples of the call; B: images per frame
+    const int B = one_pass ? 2 * S : S, T = clip ? c.frames : 1, n = T * B, fi = one_pass ? B : 0;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
     int h = c.height, w = c.width;
     Ref x = mirror;
@@ -518,13 +576,22 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
         Op op;
         op.kind = frames ? (clip ? CLIP_CROP : CROP) : !clip ? TO_NHWC : mirrored ? CLIP_TO_NHWC_FLIP : CLIP_TO_NHWC;
         op.out = x;
-        if (frames && g.flip) {
+        Ref half = x;                            // one pass: where the mirrored half of the first frame starts
+        half.elems = (size_t)S * h * w * 4;
+        if (frames && one_pass) {
+            op.aux = half;
+        } else if (frames && g.flip) {
             mirror.id = p.tensor(n, h, w, 4);
             op.aux = mirror;
         }
         op.ext = X;
-        op.n = B; op.frames = T; op.ch = 3;
+        op.n = S; op.frames = T; op.ch = 3; op.fi = fi;
         p.push(op);
+        if (one_pass && !frames) {
+            op.kind = CLIP_TO_NHWC_FLIP;
+            op.out = half;
+            p.push(op);
+        }
     }
     Ref heat = trunk(p, x, n, h, w, c.output_stride, hc, true, dt);
     // _AddCenter: the pooled centre map in the heat-maps' spare pad channel; (K + 1) % 4 == 0: a hand-over tensor of rup4(K + 2)
@@ -544,9 +611,14 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
         else op.kind = !clip ? POOL : mirrored ? CLIP_POOL_FLIP : CLIP_POOL;
         op.out = z;
         op.ext = CENTER;
-        op.n = B; op.frames = T;
+        op.n = S; op.frames = T; op.fi = fi;
         op.src_h = c.height; op.src_w = c.width; op.coff = hc;
         p.push(op);
+        if (one_pass) {
+            op.kind = frames ? CLIP_CENTER_POOL_FLIP : CLIP_POOL_FLIP;
+            op.out.elems += (size_t)S * h * w * ldz;
+            p.push(op);
+        }
     }
     // the recurrence: cell / hide of all frames as rows of two frame-major tensors (the head reads the hidden states as one)
     Ref cells, hides;
@@ -616,7 +688,7 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
     return r;
 }
 
-static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g, int dt) {
+static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& g, int dt, bool one_pass) {
     const bool clip = g.input == IN_CLIP || g.input == IN_CLIP_FRAMES;
     const int B = c.batch, T = clip ? c.frames : 1;
     const int hc = c.num_classes + 1, cg = c.num_classes + 2, ldo = rup4(cg);
@@ -624,9 +696,18 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& 
     p.dt = dt;
     p.grow_tail = dt == UP_DT_BF16;      // measured on the figures: every program of a bf16 plan needs less with it (B = 8, T = 5, 368 x 368:
                                          // 520 MB against 607 MB; the fp32 plan 1148 MB), so it is set; fp32 plans keep their layout
-    const LstmPass a = lstm_pass(p, c, g, false, mirror, dt);
+    LstmPass a = lstm_pass(p, c, g, false, mirror, dt, g.flip && one_pass);
     Op op;
-    if (g.flip) {
+    if (g.flip && one_pass) {                  // the two halves of every frame of conv5's output into a compact frame-major tensor
+        const int ld = p.tensors[a.y.id].c;
+        op.kind = CLIP_MERGE;
+        op.in = a.y; op.aux = a.y;
+        op.aux.elems += (size_t)B * a.h * a.w * ld;
+        op.out.id = p.tensor(T * B, a.h, a.w, ld);
+        op.n = B; op.frames = T; op.ch = hc;
+        p.push(op);
+        a.y = op.out;
+    } else if (g.flip) {
         const LstmPass m = lstm_pass(p, c, g, true, mirror, dt);
         op.kind = MERGE;                       // in place (NHWC): out == a with equal strides; both passes are frame-major
         op.in = a.y; op.aux = m.y; op.out = a.y;
@@ -793,7 +874,11 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             e = up_avgpool9s8_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case CLIP_POOL:
-            e = up_clip_avgpool9s8_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
+            if (op.fi)
+                e = up_clip_avgpool9s8_fwd_strided(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
+                                                   op.fi, 0, stream);
+            else
+                e = up_clip_avgpool9s8_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case LSTM0:
             e = up_lstm0_fwd(ptr(op.in), i.c, ptr(op.out), ptr(op.res), o.c, (int64_t)op.n * i.h * i.w, op.ch, stream);
@@ -803,16 +888,31 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
                             op.ch, stream);
             break;
         case CLIP_TO_NHWC:
-            e = up_clip_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
+            if (op.fi)
+                e = up_clip_nchw_to_nhwc_strided(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, op.fi, 0, stream);
+            else
+                e = up_clip_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
             break;
         case CLIP_TO_NCHW:
             e = up_clip_nhwc_to_nchw(ptr(op.in), i.c, io.out(op.ext), op.n, op.frames, op.ch, i.h, i.w, stream);
             break;
         case CLIP_TO_NHWC_FLIP:
-            e = up_clip_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
+            if (op.fi)
+                e = up_clip_nchw_to_nhwc_flip_strided(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, op.fi, 0, stream);
+            else
+                e = up_clip_nchw_to_nhwc_flip(io.in(op.ext), ptr(op.out), op.n, op.frames, op.ch, o.h, o.w, o.c, stream);
             break;
         case CLIP_POOL_FLIP:
-            e = up_clip_avgpool9s8_flip_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
+            if (op.fi)
+                e = up_clip_avgpool9s8_flip_fwd_strided(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h,
+                                                        o.w, op.fi, 0, stream);
+            else
+                e = up_clip_avgpool9s8_flip_fwd(io.in(op.ext), ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
+                                                stream);
+            break;
+        case CLIP_MERGE:       // frame t: images t * 2 B + b of `in` and of `aux` (B images on) into image t * B + b of `out`
+            e = up_clip_flip_merge(ptr(op.in), ptr(op.aux), 2 * op.n * image, image, 1, i.c, op.n, op.frames, op.ch, i.h, i.w, io.perm,
+                                   ptr(op.out), op.n * image, image, 1, i.c, stream);
             break;
         case CLIP_DECODE:
             e = up_clip_heatmap_decode(ptr(op.in), image, 1, i.c, op.n, op.frames, op.ch, i.h, i.w, io.dec_h, io.dec_w, io.idx, io.preds,
@@ -823,18 +923,32 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
                                     io.coords, io.maxvals, stream);
             break;
         case CLIP_CROP:
-            e = up_clip_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.ch, io.frame_of, io.valid_hw, io.crop_inv, op.n,
-                                     op.frames, io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), o.h, o.w, o.c, stream);
+            if (op.fi)
+                e = up_clip_crop_to_nhwc_strided(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.ch, io.frame_of, io.valid_hw,
+                                                 io.crop_inv, op.n, op.frames, io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), o.h,
+                                                 o.w, o.c, op.fi, 0, stream);
+            else
+                e = up_clip_crop_to_nhwc(io.src, io.src_type, io.frames, io.src_h, io.src_w, op.ch, io.frame_of, io.valid_hw, io.crop_inv,
+                                         op.n, op.frames, io.border, io.mean, io.stdv, ptr(op.out), ptr(op.aux), o.h, o.w, o.c, stream);
             break;
         case CENTER_POOL:
             e = up_center_pool(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.src_h, op.src_w, o.h, o.w, stream);
             break;
         case CLIP_CENTER_POOL:
-            e = up_clip_center_pool(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w, stream);
+            if (op.fi)
+                e = up_clip_center_pool_strided(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h,
+                                                o.w, op.fi, 0, stream);
+            else
+                e = up_clip_center_pool(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
+                                        stream);
             break;
         case CLIP_CENTER_POOL_FLIP:
-            e = up_clip_center_pool_flip(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
-                                         stream);
+            if (op.fi)
+                e = up_clip_center_pool_flip_strided(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w,
+                                                     o.h, o.w, op.fi, 0, stream);
+            else
+                e = up_clip_center_pool_flip(io.center_xy, io.sigma, ptr(op.out), o.c, op.coff, op.n, op.frames, op.src_h, op.src_w, o.h, o.w,
+                                             stream);
             break;
         case STATE_IN:                         // whole padded rows: the pad channels stay the zeros the plan wrote
             e = up_copy2d(io.state + op.half * io.state_half, o.c, ptr(op.out), o.c, (int64_t)o.n * o.h * o.w, o.c, stream);
@@ -1019,6 +1133,7 @@ struct up_unipose_plan {
     up_unipose_config cfg;
     Plan prog[IMAGE_FORMS];    // as IMAGE_PROGRAMS lists them
     int dtype = UP_DT_F32;     // the storage behind the stem: activations in the workspace and the packed weight images
+    int flags = 0;             // UP_PLAN_*: how the flip rows are built
     plan::Weights w;           // the listed convolutions are those of program 0: the 116 of the forward, wasp.conv2 twice
     size_t ws_bytes = 0;       // the largest of the programs that count toward it, and ...
     size_t flip_ws_bytes = 0;  // ... toward the flip test's
@@ -1031,9 +1146,16 @@ extern "C" int up_unipose_plan_create(const up_unipose_config* cfg, up_unipose_p
 extern "C" int up_unipose_plan_dtype(const up_unipose_plan* pl) { return pl ? pl->dtype : UP_ERR_INVALID; }
 
 extern "C" int up_unipose_plan_create_t(const up_unipose_config* cfg, int dtype, up_unipose_plan** out) {
+    return up_unipose_plan_create_ex(cfg, dtype, 0, out);
+}
+
+extern "C" int up_unipose_plan_flags(const up_unipose_plan* pl) { return pl ? pl->flags : UP_ERR_INVALID; }
+
+extern "C" int up_unipose_plan_create_ex(const up_unipose_config* cfg, int dtype, int flags, up_unipose_plan** out) {
     UP_REQUIRE(cfg && out, UP_ERR_INVALID, "unipose_plan_create: null argument");
     UP_REQUIRE(dtype == UP_DT_F32 || dtype == UP_DT_BF16, UP_ERR_INVALID, "unipose_plan_create: storage type %d (UP_DT_F32 or UP_DT_BF16)",
                dtype);
+    UP_REQUIRE((flags & ~UP_PLAN_FLIP_ONE_PASS) == 0, UP_ERR_INVALID, "unipose_plan_create: flags %d (UP_PLAN_FLIP_ONE_PASS or 0)", flags);
     UP_REQUIRE(cfg->batch > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->out_channels > 0, UP_ERR_INVALID,
                "unipose_plan_create: batch %d, input %dx%d, %d output channels", cfg->batch, cfg->height, cfg->width, cfg->out_channels);
     UP_REQUIRE(cfg->output_stride == 16 || cfg->output_stride == 8, UP_ERR_UNSUPPORTED,
@@ -1042,9 +1164,10 @@ extern "C" int up_unipose_plan_create_t(const up_unipose_config* cfg, int dtype,
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_plan_create: out of host memory");
     pl->cfg = *cfg;
     pl->dtype = dtype;
+    pl->flags = flags;
     for (size_t f = 0; f < IMAGE_FORMS; ++f) {
         const plan::Program& g = plan::IMAGE_PROGRAMS[f];
-        plan::build(pl->prog[f], pl->cfg, g, dtype);
+        plan::build(pl->prog[f], pl->cfg, g, dtype, (flags & UP_PLAN_FLIP_ONE_PASS) != 0);
         if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
         if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
     }
@@ -1250,6 +1373,7 @@ struct up_unipose_lstm_plan {
     up_unipose_lstm_config cfg;
     Plan prog[LSTM_FORMS];     // as LSTM_PROGRAMS lists them
     int dtype = UP_DT_F32;     // the trunk's storage: its activations and packed weight images; state, head and all I/O are fp32
+    int flags = 0;             // UP_PLAN_*: how the flip rows are built
     plan::Weights w;
     size_t ws_bytes = 0;       // the largest of the programs without the flip test
     size_t flip_ws_bytes = 0;  // the largest of those with it
@@ -1263,9 +1387,17 @@ extern "C" int up_unipose_lstm_plan_create(const up_unipose_lstm_config* cfg, up
 extern "C" int up_unipose_lstm_plan_dtype(const up_unipose_lstm_plan* pl) { return pl ? pl->dtype : UP_ERR_INVALID; }
 
 extern "C" int up_unipose_lstm_plan_create_t(const up_unipose_lstm_config* cfg, int dtype, up_unipose_lstm_plan** out) {
+    return up_unipose_lstm_plan_create_ex(cfg, dtype, 0, out);
+}
+
+extern "C" int up_unipose_lstm_plan_flags(const up_unipose_lstm_plan* pl) { return pl ? pl->flags : UP_ERR_INVALID; }
+
+extern "C" int up_unipose_lstm_plan_create_ex(const up_unipose_lstm_config* cfg, int dtype, int flags, up_unipose_lstm_plan** out) {
     UP_REQUIRE(cfg && out, UP_ERR_INVALID, "unipose_lstm_plan_create: null argument");
     UP_REQUIRE(dtype == UP_DT_F32 || dtype == UP_DT_BF16, UP_ERR_INVALID,
                "unipose_lstm_plan_create: storage type %d (UP_DT_F32 or UP_DT_BF16)", dtype);
+    UP_REQUIRE((flags & ~UP_PLAN_FLIP_ONE_PASS) == 0, UP_ERR_INVALID, "unipose_lstm_plan_create: flags %d (UP_PLAN_FLIP_ONE_PASS or 0)",
+               flags);
     UP_REQUIRE(cfg->batch > 0 && cfg->frames > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->num_classes > 0, UP_ERR_INVALID,
                "unipose_lstm_plan_create: batch %d, %d frames, input %dx%d, %d classes", cfg->batch, cfg->frames, cfg->height,
                cfg->width, cfg->num_classes);
@@ -1282,9 +1414,10 @@ extern "C" int up_unipose_lstm_plan_create_t(const up_unipose_lstm_config* cfg, 
     UP_REQUIRE(pl, UP_ERR_INVALID, "unipose_lstm_plan_create: out of host memory");
     pl->cfg = *cfg;
     pl->dtype = dtype;
+    pl->flags = flags;
     for (size_t f = 0; f < LSTM_FORMS; ++f) {
         const plan::Program& g = plan::LSTM_PROGRAMS[f];
-        plan::build_lstm(pl->prog[f], pl->cfg, g, dtype);
+        plan::build_lstm(pl->prog[f], pl->cfg, g, dtype, (flags & UP_PLAN_FLIP_ONE_PASS) != 0);
         if (g.counts == plan::COUNTS_PLAIN) pl->ws_bytes = std::max(pl->ws_bytes, pl->prog[f].ws_bytes);
         if (g.counts == plan::COUNTS_FLIP) pl->flip_ws_bytes = std::max(pl->flip_ws_bytes, pl->prog[f].ws_bytes);
         for (const plan::Op& op : pl->prog[f].ops)       // the hidden state STATE_OUT copies: its tensor's padded size

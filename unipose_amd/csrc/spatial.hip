@@ -50,23 +50,43 @@ __device__ __forceinline__ int64_t clip_image(int64_t f, int B, int T) {      //
     const int64_t t = f / B;
     return (f - t * B) * T + t;
 }
+// The _strided entries (the one-pass flip test of the video plan): frames of FI >= B images, the B samples of a launch from image
+// `first` of each on, so the image written for frame-major f = t * B + b is t * FI + first + b.  Every clip kernel that writes
+// frame-major images comes in both forms around ONE device function; STRIDED = false is f itself, the launch as it always was.
+template <bool STRIDED>
+__device__ __forceinline__ int64_t clip_dest(int64_t f, int B, int FI, int first) {
+    if (!STRIDED) return f;
+    const int64_t t = f / B;
+    return t * FI + first + (f - t * B);
+}
 // FLIP: the mirror folded in (the flip test of the video plan): the NHWC pixel (h, w) takes the NCHW pixel (h, W - 1 - w)
-template <bool FLIP>
-__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_kernel(const float* x, float* y, int B, int T, int C, int W, int HW, int ld,
-                                                                int64_t npix) {
+template <bool FLIP, bool STRIDED>
+__device__ __forceinline__ void clip_nchw_to_nhwc_body(const float* x, float* y, int B, int T, int C, int W, int HW, int ld,
+                                                       int64_t npix, int FI, int first) {
     UP_GRID_STRIDE(i, npix) {
         const int64_t f = i / HW;
-        int hw = (int)(i - f * HW);
+        const int pix = (int)(i - f * HW);
+        int hw = pix;
         if (FLIP) {
             const int h = hw / W;
             hw = h * W + (W - 1 - (hw - h * W));
         }
         const float* src = x + clip_image(f, B, T) * C * HW + hw;
-        float* dst = y + i * ld;
+        float* dst = y + (STRIDED ? clip_dest<true>(f, B, FI, first) * HW + pix : i) * ld;
         for (int c = 0; c < ld; c += 4)
             *reinterpret_cast<float4*>(dst + c) =
                 make_float4(nchw_at(src, C, HW, c), nchw_at(src, C, HW, c + 1), nchw_at(src, C, HW, c + 2), nchw_at(src, C, HW, c + 3));
     }
+}
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_kernel(const float* x, float* y, int B, int T, int C, int W, int HW, int ld,
+                                                                int64_t npix) {
+    clip_nchw_to_nhwc_body<FLIP, false>(x, y, B, T, C, W, HW, ld, npix, B, 0);
+}
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_nchw_to_nhwc_strided_kernel(const float* x, float* y, int B, int T, int C, int W, int HW,
+                                                                        int ld, int64_t npix, int FI, int first) {
+    clip_nchw_to_nhwc_body<FLIP, true>(x, y, B, T, C, W, HW, ld, npix, FI, first);
 }
 __global__ void __launch_bounds__(256) clip_nhwc_to_nchw_kernel(const float* x, int ld, float* y, int B, int T, int C, int HW,
                                                                 int64_t npix) {
@@ -403,16 +423,27 @@ __global__ void __launch_bounds__(256) avgpool9s8_kernel(const float* x, float* 
     }
 }
 // ... of a clip's (B, T, 1, H, W) centre maps into channel coff of the frame-major (T * B, P, Q, ldy) hand-over tensor
-template <bool FLIP>
-__global__ void __launch_bounds__(256) clip_avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int B, int T, int H,
-                                                              int W, int P, int Q, int64_t total) {
+template <bool FLIP, bool STRIDED>
+__device__ __forceinline__ void clip_avgpool9s8_body(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P,
+                                                     int Q, int64_t total, int FI, int first) {
     UP_GRID_STRIDE(i, total) {
         int q = (int)(i % Q);
         int64_t t = i / Q;
         int p = (int)(t % P);
         int64_t f = t / P;
-        y[i * ldy + coff] = avgpool9s8_at<FLIP>(x + clip_image(f, B, T) * H * W, H, W, p, q);
+        const int64_t o = STRIDED ? (clip_dest<true>(f, B, FI, first) * P + p) * Q + q : i;
+        y[o * ldy + coff] = avgpool9s8_at<FLIP>(x + clip_image(f, B, T) * H * W, H, W, p, q);
     }
+}
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_avgpool9s8_kernel(const float* x, float* y, int ldy, int coff, int B, int T, int H,
+                                                              int W, int P, int Q, int64_t total) {
+    clip_avgpool9s8_body<FLIP, false>(x, y, ldy, coff, B, T, H, W, P, Q, total, B, 0);
+}
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_avgpool9s8_strided_kernel(const float* x, float* y, int ldy, int coff, int B, int T, int H,
+                                                                      int W, int P, int Q, int64_t total, int FI, int first) {
+    clip_avgpool9s8_body<FLIP, true>(x, y, ldy, coff, B, T, H, W, P, Q, total, FI, first);
 }
 
 // ---- ConvLSTM gates -------------------------------------------------------------------------
@@ -836,9 +867,9 @@ __global__ void __launch_bounds__(256) gaussian_map_kernel(const double* center,
 // statement, so it is the value target_gauss would test; a skipped tap adds the +0.0f target_gauss would have returned.  A NaN
 // centre gives a NaN d2, which fails the comparison and is evaluated: NaN propagates.  An infinite centre gives d2 = inf: skipped
 // as the 0 that exp(-inf) is (at a sigma so large that the bound is inf too, it is evaluated).
-template <bool CLIP, bool FLIP>
-__global__ void __launch_bounds__(256) center_pool_kernel(const double* center, double sigma, double skip, float* y, int ldy, int coff,
-                                                          int B, int T, int H, int W, int P, int Q, int64_t total) {
+template <bool CLIP, bool FLIP, bool STRIDED>
+__device__ __forceinline__ void center_pool_body(const double* center, double sigma, double skip, float* y, int ldy, int coff, int B,
+                                                 int T, int H, int W, int P, int Q, int64_t total, int FI, int first) {
     UP_GRID_STRIDE(i, total) {
         const int q = (int)(i % Q);
         const int64_t t = i / Q;
@@ -846,12 +877,24 @@ __global__ void __launch_bounds__(256) center_pool_kernel(const double* center, 
         const int64_t f = t / P;
         const int64_t n = CLIP ? clip_image(f, B, T) : f;
         const double cx = center[2 * n], cy = center[2 * n + 1];
-        y[i * ldy + coff] = avgpool9s8_window<FLIP>(H, W, p, q, [=](int h, int c) {
+        const int64_t o = STRIDED ? (clip_dest<true>(f, B, FI, first) * P + p) * Q + q : i;
+        y[o * ldy + coff] = avgpool9s8_window<FLIP>(H, W, p, q, [=](int h, int c) {
             const double dx = (double)c - cx, dy = (double)h - cy;
             const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
             return d2 > skip ? 0.f : target_gauss((double)c, (double)h, cx, cy, sigma);
         });
     }
+}
+template <bool CLIP, bool FLIP>
+__global__ void __launch_bounds__(256) center_pool_kernel(const double* center, double sigma, double skip, float* y, int ldy, int coff,
+                                                          int B, int T, int H, int W, int P, int Q, int64_t total) {
+    center_pool_body<CLIP, FLIP, false>(center, sigma, skip, y, ldy, coff, B, T, H, W, P, Q, total, B, 0);
+}
+template <bool FLIP>
+__global__ void __launch_bounds__(256) clip_center_pool_strided_kernel(const double* center, double sigma, double skip, float* y, int ldy,
+                                                                       int coff, int B, int T, int H, int W, int P, int Q, int64_t total,
+                                                                       int FI, int first) {
+    center_pool_body<true, FLIP, true>(center, sigma, skip, y, ldy, coff, B, T, H, W, P, Q, total, FI, first);
 }
 // Box-head targets (getBoundingBox, lsp_lspet_data.py:71-113 / bbc_data.py:23-72), every statement in float64 like Python's
 // floats; int() is trunc().  The reference calls the SECOND coordinate x and the first y, bounds x by `width` and y by `height`,
@@ -981,16 +1024,18 @@ __global__ void __launch_bounds__(256) augment_image_kernel(const T* src, int Hs
 // instruction, forwards into y and backwards into y_flip; the quads beyond the first are the zero pad channels.
 // CLIP (up_clip_crop_to_nhwc): the outputs are frame-major, image t * cB + b holds sample b * cT + t of the batch-major frame_of
 // and inv; everything else is the same code.
-template <typename T, bool CLIP>
-__global__ void __launch_bounds__(256) crop_to_nhwc_kernel(const T* src, int F, int Hs, int Ws, int C, const int32_t* frame_of,
-                                                           const int32_t* valid_hw, const double* inv, float border, float mean,
-                                                           float stdv, float* y, float* yf, int Ho, int Wo, int ld,
-                                                           long long total /* B*Ho*Wo */, int cB, int cT) {
-    UP_GRID_STRIDE(e, total) {
-        const int u = (int)(e % Wo);
-        const int64_t t = e / Wo;
+// STRIDED (up_clip_crop_to_nhwc_strided): image t * FI + first + b of both outputs; the source is read once all the same.
+template <typename T, bool CLIP, bool STRIDED>
+__device__ __forceinline__ void crop_to_nhwc_body(const T* src, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                                  const int32_t* valid_hw, const double* inv, float border, float mean, float stdv,
+                                                  float* y, float* yf, int Ho, int Wo, int ld, long long total /* B*Ho*Wo */, int cB,
+                                                  int cT, int FI, int first) {
+    UP_GRID_STRIDE(e0, total) {
+        const int u = (int)(e0 % Wo);
+        const int64_t t = e0 / Wo;
         const int v = (int)(t % Ho);
-        const int64_t b = CLIP ? clip_image(t / Ho, cB, cT) : t / Ho;     // the sample; e stays the output pixel
+        const int64_t b = CLIP ? clip_image(t / Ho, cB, cT) : t / Ho;     // the sample; e is the output pixel
+        const int64_t e = STRIDED ? (clip_dest<true>(t / Ho, cB, FI, first) * Ho + v) * Wo + u : e0;
         int64_t f = frame_of ? (int64_t)frame_of[b] : b;
         int Hv = 0, Wv = 0;
         if (f >= 0 && f < F) {
@@ -1017,6 +1062,23 @@ __global__ void __launch_bounds__(256) crop_to_nhwc_kernel(const T* src, int F, 
             for (int c = 4; c < ld; c += 4) *reinterpret_cast<float4*>(d + c) = z;
         }
     }
+}
+template <typename T, bool CLIP>
+__global__ void __launch_bounds__(256) crop_to_nhwc_kernel(const T* src, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                                           const int32_t* valid_hw, const double* inv, float border, float mean,
+                                                           float stdv, float* y, float* yf, int Ho, int Wo, int ld,
+                                                           long long total /* B*Ho*Wo */, int cB, int cT) {
+    crop_to_nhwc_body<T, CLIP, false>(src, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y, yf, Ho, Wo, ld, total, cB, cT,
+                                      cB, 0);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) clip_crop_to_nhwc_strided_kernel(const T* src, int F, int Hs, int Ws, int C,
+                                                                        const int32_t* frame_of, const int32_t* valid_hw,
+                                                                        const double* inv, float border, float mean, float stdv,
+                                                                        float* y, float* yf, int Ho, int Wo, int ld, long long total,
+                                                                        int cB, int cT, int FI, int first) {
+    crop_to_nhwc_body<T, true, true>(src, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y, yf, Ho, Wo, ld, total, cB, cT, FI,
+                                     first);
 }
 
 // ---- PCK / PCKh accuracy on joint coordinates (utils/evaluate.py:5-29,58-172) -------------------------------------
@@ -1133,10 +1195,12 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_flip_kernel(const float* x, 
 struct FlipPerm {
     uint8_t v[256];
 };
-template <bool JFAST>
-__global__ void __launch_bounds__(256) flip_merge_kernel(const float* a, const float* f, int64_t isb, int64_t isj, int64_t isp,
-                                                         int J, int H, int W, FlipPerm perm, float* out, int64_t osb, int64_t osj,
-                                                         int64_t osp, int64_t total) {
+// CLIP (up_clip_flip_merge): a two-level batch index, image t * B + b of the walk read at t * ist + b * isb and written at
+// t * ost + b * osb — the two halves of a 2B-wide frame-major tensor merged into a compact one; else ist / ost / B are not read.
+template <bool JFAST, bool CLIP>
+__device__ __forceinline__ void flip_merge_body(const float* a, const float* f, int64_t ist, int64_t isb, int64_t isj, int64_t isp,
+                                                int B, int J, int H, int W, const FlipPerm& perm, float* out, int64_t ost, int64_t osb,
+                                                int64_t osj, int64_t osp, int64_t total) {
     const int HW = H * W;
     UP_GRID_STRIDE(i, total) {
         int64_t b;
@@ -1153,10 +1217,28 @@ __global__ void __launch_bounds__(256) flip_merge_kernel(const float* a, const f
             j = (int)(bj - b * J);
         }
         const int y = pix / W, x = pix - y * W;
-        const float va = a[b * isb + j * isj + pix * isp];
-        const float vf = f[b * isb + (int64_t)perm.v[j] * isj + (int64_t)(y * W + (W - 1 - x)) * isp];
-        out[b * osb + j * osj + pix * osp] = __fmul_rn(0.5f, va + vf);
+        int64_t ib = b * isb, ob = b * osb;
+        if (CLIP) {
+            const int64_t t = b / B, s = b - t * B;
+            ib = t * ist + s * isb;
+            ob = t * ost + s * osb;
+        }
+        const float va = a[ib + j * isj + pix * isp];
+        const float vf = f[ib + (int64_t)perm.v[j] * isj + (int64_t)(y * W + (W - 1 - x)) * isp];
+        out[ob + j * osj + pix * osp] = __fmul_rn(0.5f, va + vf);
     }
+}
+template <bool JFAST>
+__global__ void __launch_bounds__(256) flip_merge_kernel(const float* a, const float* f, int64_t isb, int64_t isj, int64_t isp,
+                                                         int J, int H, int W, FlipPerm perm, float* out, int64_t osb, int64_t osj,
+                                                         int64_t osp, int64_t total) {
+    flip_merge_body<JFAST, false>(a, f, 0, isb, isj, isp, 1, J, H, W, perm, out, 0, osb, osj, osp, total);
+}
+template <bool JFAST>
+__global__ void __launch_bounds__(256) clip_flip_merge_kernel(const float* a, const float* f, int64_t ist, int64_t isb, int64_t isj,
+                                                              int64_t isp, int B, int J, int H, int W, FlipPerm perm, float* out,
+                                                              int64_t ost, int64_t osb, int64_t osj, int64_t osp, int64_t total) {
+    flip_merge_body<JFAST, true>(a, f, ist, isb, isj, isp, B, J, H, W, perm, out, ost, osb, osj, osp, total);
 }
 
 // final_preds (utils/extra_utils/evaluation.py:75-97): one wavefront per (b, j) map like argmax_kernel, then lane 0 does the
@@ -1267,21 +1349,49 @@ extern "C" int up_nhwc_to_nchw(const float* x, int ldx, float* y, int N, int C, 
     return up_nhwc_to_nchw_t(x, ldx, y, N, C, H, W, UP_DT_F32, stream);
 }
 
-extern "C" int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream) {
+// what every _strided clip entry asks of its two extra arguments, after its neighbour's own checks (B, T > 0): the B samples lie
+// inside a frame of frame_images images, and the image index t * frame_images + first + b stays an int32
+static int clip_stride_ok(const char* what, int B, int T, int frame_images, int first) {
+    UP_REQUIRE(first >= 0 && (int64_t)frame_images >= (int64_t)first + B, UP_ERR_INVALID,
+               "%s: %d samples from image %d of frames of %d images", what, B, first, frame_images);
+    UP_REQUIRE((int64_t)T * frame_images <= INT32_MAX, UP_ERR_INVALID, "%s: %d frames of %d images: an image index beyond the int32 range",
+               what, T, frame_images);
+    return UP_OK;
+}
+// the four layout entries: one set of refusals, one device function (strided: the kernel that takes frame_images and first)
+static int clip_nchw_to_nhwc(const char* what, bool flip, bool strided, const float* x, float* y, int B, int T, int C, int H, int W, int ldy,
+                             int frame_images, int first, void* stream) {
     UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldy >= C && ldy % 4 == 0 && (uintptr_t)y % 16 == 0,
-               UP_ERR_INVALID, "clip_nchw_to_nhwc: bad argument");
+               UP_ERR_INVALID, "%s: bad argument", what);
+    if (flip) UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "%s: %d x %d: a pixel index beyond the int32 range", what, H, W);
+    if (strided)
+        if (int e = clip_stride_ok(what, B, T, frame_images, first)) return e;
     int64_t npix = (int64_t)T * B * H * W;
-    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<false>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
-    return check_launch("clip_nchw_to_nhwc");
+    if (strided && flip)
+        UP_LAUNCH_1D(clip_nchw_to_nhwc_strided_kernel<true>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix, frame_images,
+                     first);
+    else if (strided)
+        UP_LAUNCH_1D(clip_nchw_to_nhwc_strided_kernel<false>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix, frame_images,
+                     first);
+    else if (flip)
+        UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<true>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
+    else
+        UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<false>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
+    return check_launch(what);
+}
+extern "C" int up_clip_nchw_to_nhwc(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream) {
+    return clip_nchw_to_nhwc("clip_nchw_to_nhwc", false, false, x, y, B, T, C, H, W, ldy, B, 0, stream);
 }
 extern "C" int up_clip_nchw_to_nhwc_flip(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, void* stream) {
-    UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldy >= C && ldy % 4 == 0 && (uintptr_t)y % 16 == 0,
-               UP_ERR_INVALID, "clip_nchw_to_nhwc_flip: bad argument");
-    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "clip_nchw_to_nhwc_flip: %d x %d: a pixel index beyond the int32 range", H,
-               W);
-    int64_t npix = (int64_t)T * B * H * W;
-    UP_LAUNCH_1D(clip_nchw_to_nhwc_kernel<true>, npix, as_stream(stream), x, y, B, T, C, W, H * W, ldy, npix);
-    return check_launch("clip_nchw_to_nhwc_flip");
+    return clip_nchw_to_nhwc("clip_nchw_to_nhwc_flip", true, false, x, y, B, T, C, H, W, ldy, B, 0, stream);
+}
+extern "C" int up_clip_nchw_to_nhwc_strided(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, int frame_images,
+                                            int first, void* stream) {
+    return clip_nchw_to_nhwc("clip_nchw_to_nhwc_strided", false, true, x, y, B, T, C, H, W, ldy, frame_images, first, stream);
+}
+extern "C" int up_clip_nchw_to_nhwc_flip_strided(const float* x, float* y, int B, int T, int C, int H, int W, int ldy, int frame_images,
+                                                 int first, void* stream) {
+    return clip_nchw_to_nhwc("clip_nchw_to_nhwc_flip_strided", true, true, x, y, B, T, C, H, W, ldy, frame_images, first, stream);
 }
 extern "C" int up_clip_nhwc_to_nchw(const float* x, int ldx, float* y, int B, int T, int C, int H, int W, void* stream) {
     UP_REQUIRE(x && y && B > 0 && T > 0 && C > 0 && H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && (uintptr_t)x % 16 == 0,
@@ -1471,16 +1581,37 @@ extern "C" int up_clip_avgpool9s8_fwd(const float* x, float* y, int ldy, int cof
     return check_launch("clip_avgpool9s8");
 }
 
+// the mirrored pooling and the two _strided poolings: the refusals of up_clip_avgpool9s8_flip_fwd (which holds all of its plain
+// neighbour's, and P, Q > 0: with none of them a strided launch would have no pixel to write)
+static int clip_avgpool_checked(const char* what, bool flip, bool strided, const float* x, float* y, int ldy, int coff, int B, int T, int H,
+                                int W, int P, int Q, int frame_images, int first, void* stream) {
+    UP_REQUIRE(x && y && B > 0 && T > 0 && H > 0 && W > 0 && ldy > 0 && coff >= 0 && coff < ldy, UP_ERR_INVALID, "%s: bad argument", what);
+    UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1 && P > 0 && Q > 0, UP_ERR_INVALID, "%s: P,Q mismatch", what);
+    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "%s: %d x %d: a pixel index beyond the int32 range", what, H, W);
+    if (strided)
+        if (int e = clip_stride_ok(what, B, T, frame_images, first)) return e;
+    int64_t total = (int64_t)T * B * P * Q;
+    if (!strided)
+        UP_LAUNCH_1D(clip_avgpool9s8_kernel<true>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
+    else if (flip)
+        UP_LAUNCH_1D(clip_avgpool9s8_strided_kernel<true>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total,
+                     frame_images, first);
+    else
+        UP_LAUNCH_1D(clip_avgpool9s8_strided_kernel<false>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total,
+                     frame_images, first);
+    return check_launch(what);
+}
 extern "C" int up_clip_avgpool9s8_flip_fwd(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
                                            void* stream) {
-    UP_REQUIRE(x && y && B > 0 && T > 0 && H > 0 && W > 0 && ldy > 0 && coff >= 0 && coff < ldy, UP_ERR_INVALID,
-               "clip_avgpool_flip: bad argument");
-    UP_REQUIRE(P == (H + 2 - 9) / 8 + 1 && Q == (W + 2 - 9) / 8 + 1 && P > 0 && Q > 0, UP_ERR_INVALID,
-               "clip_avgpool_flip: P,Q mismatch");
-    UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "clip_avgpool_flip: %d x %d: a pixel index beyond the int32 range", H, W);
-    int64_t total = (int64_t)T * B * P * Q;
-    UP_LAUNCH_1D(clip_avgpool9s8_kernel<true>, total, as_stream(stream), x, y, ldy, coff, B, T, H, W, P, Q, total);
-    return check_launch("clip_avgpool9s8_flip");
+    return clip_avgpool_checked("clip_avgpool_flip", true, false, x, y, ldy, coff, B, T, H, W, P, Q, B, 0, stream);
+}
+extern "C" int up_clip_avgpool9s8_fwd_strided(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P, int Q,
+                                              int frame_images, int first, void* stream) {
+    return clip_avgpool_checked("clip_avgpool_strided", false, true, x, y, ldy, coff, B, T, H, W, P, Q, frame_images, first, stream);
+}
+extern "C" int up_clip_avgpool9s8_flip_fwd_strided(const float* x, float* y, int ldy, int coff, int B, int T, int H, int W, int P,
+                                                   int Q, int frame_images, int first, void* stream) {
+    return clip_avgpool_checked("clip_avgpool_flip_strided", true, true, x, y, ldy, coff, B, T, H, W, P, Q, frame_images, first, stream);
 }
 
 extern "C" int up_lstm0_fwd(const float* gates, int ldg, float* cell, float* hide, int ldo, int64_t rows, int Cg,
@@ -1616,6 +1747,46 @@ extern "C" int up_flip_merge(const float* a, const float* f, int64_t in_stride_b
     return check_launch("flip_merge");
 }
 
+// up_flip_merge over T * B images behind a two-level batch index (include/unipose_hip.h): the same device function, the same checks
+extern "C" int up_clip_flip_merge(const float* a, const float* f, int64_t in_stride_t, int64_t in_stride_b, int64_t in_stride_j,
+                                  int64_t in_stride_p, int B, int T, int J, int H, int W, const int32_t* perm_host, float* out,
+                                  int64_t out_stride_t, int64_t out_stride_b, int64_t out_stride_j, int64_t out_stride_p, void* stream) {
+    UP_REQUIRE(a && f && perm_host && out, UP_ERR_INVALID, "clip_flip_merge: null argument");
+    UP_REQUIRE(B > 0 && T > 0 && J > 0 && H > 0 && W > 0 && in_stride_t > 0 && in_stride_b > 0 && in_stride_j > 0 && in_stride_p > 0 &&
+                   out_stride_t > 0 && out_stride_b > 0 && out_stride_j > 0 && out_stride_p > 0,
+               UP_ERR_INVALID, "clip_flip_merge: %d x %d x %d maps of %d x %d, strides %lld / %lld / %lld / %lld -> %lld / %lld / %lld / %lld",
+               T, B, J, H, W, (long long)in_stride_t, (long long)in_stride_b, (long long)in_stride_j, (long long)in_stride_p,
+               (long long)out_stride_t, (long long)out_stride_b, (long long)out_stride_j, (long long)out_stride_p);
+    UP_REQUIRE(J <= 256, UP_ERR_UNSUPPORTED, "clip_flip_merge: %d channels (the permutation travels as 256 bytes of kernel arguments)", J);
+    FlipPerm perm;
+    memset(&perm, 0, sizeof(perm));
+    for (int j = 0; j < J; ++j) {
+        UP_REQUIRE(perm_host[j] >= 0 && perm_host[j] < J, UP_ERR_INVALID, "clip_flip_merge: perm[%d] = %d outside 0..%d", j,
+                   (int)perm_host[j], J - 1);
+        perm.v[j] = (uint8_t)perm_host[j];
+    }
+    UP_REQUIRE(out != f, UP_ERR_INVALID, "clip_flip_merge: out == f (the mirrored reads cross threads)");
+    UP_REQUIRE(out != a || (out_stride_t == in_stride_t && out_stride_b == in_stride_b && out_stride_j == in_stride_j &&
+                            out_stride_p == in_stride_p),
+               UP_ERR_INVALID, "clip_flip_merge: out == a needs equal strides");
+    // the maps of one frame as up_flip_merge bounds them, and the frames' own offset on top, all within int32
+    const int64_t lim = INT32_MAX;
+    UP_REQUIRE(maps_in_int32(in_stride_b, in_stride_j, in_stride_p, B, J, H, W) &&
+                   maps_in_int32(out_stride_b, out_stride_j, out_stride_p, B, J, H, W) && (int64_t)T * B * J <= lim && in_stride_t <= lim &&
+                   out_stride_t <= lim &&
+                   (T - 1) * in_stride_t + (B - 1) * in_stride_b + (J - 1) * in_stride_j + ((int64_t)H * W - 1) * in_stride_p <= lim &&
+                   (T - 1) * out_stride_t + (B - 1) * out_stride_b + (J - 1) * out_stride_j + ((int64_t)H * W - 1) * out_stride_p <= lim,
+               UP_ERR_INVALID, "clip_flip_merge: %d x %d x %d maps of %d x %d: an index beyond the int32 range", T, B, J, H, W);
+    const int64_t total = (int64_t)T * B * J * H * W;
+    if (out_stride_j < out_stride_p)
+        UP_LAUNCH_1D(clip_flip_merge_kernel<true>, total, as_stream(stream), a, f, in_stride_t, in_stride_b, in_stride_j, in_stride_p, B, J,
+                     H, W, perm, out, out_stride_t, out_stride_b, out_stride_j, out_stride_p, total);
+    else
+        UP_LAUNCH_1D(clip_flip_merge_kernel<false>, total, as_stream(stream), a, f, in_stride_t, in_stride_b, in_stride_j, in_stride_p, B, J,
+                     H, W, perm, out, out_stride_t, out_stride_b, out_stride_j, out_stride_p, total);
+    return check_launch("clip_flip_merge");
+}
+
 extern "C" int up_final_preds(const float* hm, int64_t stride_b, int64_t stride_j, int64_t stride_p, int B, int J, int H, int W,
                               int res0, int res1, const double* inv, float* preds_xy, float* coords_xy, float* maxvals,
                               void* stream) {
@@ -1719,9 +1890,18 @@ static void crop_launch(const void* src_hwc, int F, int Hs, int Ws, int C, const
     hipLaunchKernelGGL((crop_to_nhwc_kernel<PIX, CLIP>), dim3(grid_cap(total)), dim3(256), 0, as_stream(stream), (const PIX*)src_hwc, F,
                        Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y, yf, Ho, Wo, ldy, total, B, T);
 }
+template <typename PIX>
+static void crop_launch_strided(const void* src_hwc, int F, int Hs, int Ws, int C, const int32_t* frame_of, const int32_t* valid_hw,
+                                const double* inv, int B, int T, float border, float mean, float stdv, float* y, float* yf, int Ho, int Wo,
+                                int ldy, long long total, int frame_images, int first, void* stream) {
+    hipLaunchKernelGGL((clip_crop_to_nhwc_strided_kernel<PIX>), dim3(grid_cap(total)), dim3(256), 0, as_stream(stream),
+                       (const PIX*)src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, border, mean, stdv, y, yf, Ho, Wo, ldy, total, B, T,
+                       frame_images, first);
+}
 static int crop_to_nhwc(const char* what, const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
                         const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv, float* y_nhwc,
-                        float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream) {
+                        float* y_flip_nhwc, int Ho, int Wo, int ldy, void* stream, bool strided = false, int frame_images = 0,
+                        int first = 0) {
     const bool clip = T != 0;
     UP_REQUIRE(src_hwc && inv, UP_ERR_INVALID, "%s: null argument", what);
     UP_REQUIRE(y_nhwc || y_flip_nhwc, UP_ERR_INVALID, "%s: both outputs are null", what);
@@ -1737,6 +1917,16 @@ static int crop_to_nhwc(const char* what, const void* src_hwc, int src_type, int
     UP_REQUIRE(frame_of || F == samples, UP_ERR_INVALID, "%s: no frame_of with %d frames for %lld samples", what, F, samples);
     UP_REQUIRE(stdv > 0.f, UP_ERR_INVALID, "%s: std %g", what, (double)stdv);
     const long long total = samples * Ho * Wo;
+    if (strided) {
+        if (int e = clip_stride_ok(what, B, T, frame_images, first)) return e;
+        if (src_type == UP_PIX_U8)
+            crop_launch_strided<uint8_t>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
+                                         ldy, total, frame_images, first, stream);
+        else
+            crop_launch_strided<float>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
+                                       ldy, total, frame_images, first, stream);
+        return check_launch(what);
+    }
     if (src_type == UP_PIX_U8) {
         if (clip)
             crop_launch<uint8_t, true>(src_hwc, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc, y_flip_nhwc, Ho, Wo,
@@ -1767,10 +1957,18 @@ extern "C" int up_clip_crop_to_nhwc(const void* src_hwc, int src_type, int F, in
     return crop_to_nhwc("clip_crop_to_nhwc", src_hwc, src_type, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv, y_nhwc,
                         y_flip_nhwc, Ho, Wo, ldy, stream);
 }
+extern "C" int up_clip_crop_to_nhwc_strided(const void* src_hwc, int src_type, int F, int Hs, int Ws, int C, const int32_t* frame_of,
+                                            const int32_t* valid_hw, const double* inv, int B, int T, float border, float mean, float stdv,
+                                            float* y_nhwc, float* y_flip_nhwc, int Ho, int Wo, int ldy, int frame_images, int first,
+                                            void* stream) {
+    UP_REQUIRE(T > 0, UP_ERR_INVALID, "clip_crop_to_nhwc_strided: %d frames per sample", T);
+    return crop_to_nhwc("clip_crop_to_nhwc_strided", src_hwc, src_type, F, Hs, Ws, C, frame_of, valid_hw, inv, B, T, border, mean, stdv,
+                        y_nhwc, y_flip_nhwc, Ho, Wo, ldy, stream, true, frame_images, first);
+}
 
 // the three centre-pool entries: one set of refusals, one kernel
 static int center_pool(const char* what, bool clip, bool flip, const double* center_xy, double sigma, float* y, int ldy, int coff, int B,
-                       int T, int H, int W, int P, int Q, void* stream) {
+                       int T, int H, int W, int P, int Q, void* stream, bool strided = false, int frame_images = 0, int first = 0) {
     UP_REQUIRE(center_xy && y, UP_ERR_INVALID, "%s: null argument", what);
     UP_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && ldy > 0, UP_ERR_INVALID, "%s: %d x %d maps of %d x %d, ldy %d", what, B, T, H, W, ldy);
     UP_REQUIRE(sigma > 0, UP_ERR_INVALID, "%s: sigma %g", what, sigma);
@@ -1779,6 +1977,16 @@ static int center_pool(const char* what, bool clip, bool flip, const double* cen
     UP_REQUIRE((int64_t)H * W <= INT32_MAX, UP_ERR_INVALID, "%s: %d x %d: a pixel index beyond the int32 range", what, H, W);
     const int64_t total = (int64_t)T * B * P * Q;
     const double skip = 9.4 * sigma * sigma;
+    if (strided) {
+        if (int e = clip_stride_ok(what, B, T, frame_images, first)) return e;
+        if (flip)
+            UP_LAUNCH_1D(clip_center_pool_strided_kernel<true>, total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P,
+                         Q, total, frame_images, first);
+        else
+            UP_LAUNCH_1D(clip_center_pool_strided_kernel<false>, total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P,
+                         Q, total, frame_images, first);
+        return check_launch(what);
+    }
     if (!clip)
         UP_LAUNCH_1D((center_pool_kernel<false, false>), total, as_stream(stream), center_xy, sigma, skip, y, ldy, coff, B, T, H, W, P, Q,
                      total);
@@ -1801,6 +2009,16 @@ extern "C" int up_clip_center_pool(const double* center_xy, double sigma, float*
 extern "C" int up_clip_center_pool_flip(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W,
                                         int P, int Q, void* stream) {
     return center_pool("clip_center_pool_flip", true, true, center_xy, sigma, y, ldy, coff, B, T, H, W, P, Q, stream);
+}
+extern "C" int up_clip_center_pool_strided(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H, int W,
+                                           int P, int Q, int frame_images, int first, void* stream) {
+    return center_pool("clip_center_pool_strided", true, false, center_xy, sigma, y, ldy, coff, B, T, H, W, P, Q, stream, true, frame_images,
+                       first);
+}
+extern "C" int up_clip_center_pool_flip_strided(const double* center_xy, double sigma, float* y, int ldy, int coff, int B, int T, int H,
+                                                int W, int P, int Q, int frame_images, int first, void* stream) {
+    return center_pool("clip_center_pool_flip_strided", true, true, center_xy, sigma, y, ldy, coff, B, T, H, W, P, Q, stream, true,
+                       frame_images, first);
 }
 
 extern "C" int up_peak_mask(const float* maps, int nmaps, int H, int W, uint8_t* mask, void* stream) {

@@ -1856,6 +1856,28 @@ def flip_merge(a: torch.Tensor, f: torch.Tensor, perm, out: torch.Tensor = None)
     return out
 
 
+def clip_flip_merge(x: torch.Tensor, perm, out: torch.Tensor = None):
+    """``flip_merge`` of the two halves of every frame of frame-major maps (``up_clip_flip_merge``): x (T, 2 B, J, H, W), images
+    [:, :B] the maps of the samples as given and [:, B:] those of the mirrored samples -> (T, B, J, H, W), one launch — equal bits to
+    ``flip_merge(x[:, :B].flatten(0, 1), x[:, B:].flatten(0, 1), perm)``.  What the one-pass flip test of ``UniPoseLSTMPlan`` runs on
+    conv5's output."""
+    _dev_ok(x, out)
+    if x.dtype != torch.float32 or x.dim() != 5 or x.shape[1] % 2 or x.shape[1] < 2:
+        raise ValueError(f"clip_flip_merge: float32 (T, 2 B, J, H, W) maps, got {tuple(x.shape)} {x.dtype}")
+    x = _dense(x.detach())
+    t, b2, j, h, w = x.shape
+    b = b2 // 2
+    if out is None:
+        out = torch.empty((t, b, j, h, w), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (t, b, j, h, w) or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"clip_flip_merge: `out` is {tuple(out.shape)} {out.dtype}, a contiguous float32 {(t, b, j, h, w)} expected")
+    image = j * h * w
+    _C.check(_C.lib().up_clip_flip_merge(x.data_ptr(), x.data_ptr() + 4 * b * image, b2 * image, image, h * w, 1, b, t, j, h, w,
+                                         _perm_array(perm, j), out.data_ptr(), b * image, image, h * w, 1, _stream(x)),
+             "clip_flip_merge")
+    return out
+
+
 def _final_preds(t, strides, b, j, h, w, center, scale, res, return_coords):
     from . import protocol
     res = [w, h] if res is None else protocol._res(res)
@@ -2017,8 +2039,9 @@ def augment_image(pixels: torch.Tensor, inv, out_hw, border: float = 128.0, mean
     return out
 
 
-def _crop_to_nhwc(who, frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, border, mean, std):
-    """``crop_to_nhwc`` (clip = None) and ``clip_crop_to_nhwc`` (clip = (B, T)): the same checks, one call each"""
+def _crop_to_nhwc(who, frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, border, mean, std, strided=None):
+    """``crop_to_nhwc`` (clip = None) and ``clip_crop_to_nhwc`` (clip = (B, T)): the same checks, one call each.  strided:
+    (frame_images, first, out, out_flip) of ``up_clip_crop_to_nhwc_strided``, the caller's tensors written in place."""
     _dev_ok(frames)
     if frames.dtype not in (torch.uint8, torch.float32):
         raise TypeError(f"{who}: uint8 or float32 frames, got {frames.dtype}")
@@ -2062,6 +2085,17 @@ def _crop_to_nhwc(who, frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, 
             raise ValueError(f"{who}: valid_hw {tuple(valid.shape)} for {nf} frames ((F, 2) expected)")
     ho, wo = int(out_hw[0]), int(out_hw[1])
     shape = (images, max(ho, 0), max(wo, 0), max(int(ld), 0))
+    if strided is not None:
+        fi, first, y, yf = strided
+        shape = (lead[1] * max(int(fi), 0),) + shape[1:]
+        for t in (y, yf):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous()):
+                raise ValueError(f"{who}: an output {tuple(t.shape)} {t.dtype}, a contiguous float32 {shape} on {x.device} expected")
+        _dev_ok(y, yf)
+        _C.check(_C.lib().up_clip_crop_to_nhwc_strided(
+            x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, h, w, c, _ptr(fo), _ptr(valid), m.data_ptr(), lead[0], lead[1],
+            float(border), float(mean), float(std), _ptr(y), _ptr(yf), ho, wo, int(ld), int(fi), int(first), _stream(x)), who)
+        return y, yf
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     yf = torch.empty(shape, dtype=torch.float32, device=x.device) if flip else None
     head = (x.data_ptr(), 0 if x.dtype == torch.uint8 else 1, nf, h, w, c, _ptr(fo), _ptr(valid), m.data_ptr())
@@ -2096,13 +2130,26 @@ def clip_crop_to_nhwc(frames: torch.Tensor, inv, out_hw, clip, frame_of=None, va
     return _crop_to_nhwc("clip_crop_to_nhwc", frames, inv, out_hw, clip, frame_of, valid_hw, flip, ld, border, mean, std)
 
 
+def clip_crop_to_nhwc_strided(frames: torch.Tensor, inv, out_hw, clip, frame_images: int, first: int, out: torch.Tensor = None,
+                              out_flip: torch.Tensor = None, frame_of=None, valid_hw=None, ld: int = 4, border: float = 128.0,
+                              mean: float = 128.0, std: float = 256.0):
+    """``clip_crop_to_nhwc`` into frames of `frame_images` >= B images (``up_clip_crop_to_nhwc_strided``): the crop of sample (b, t)
+    goes to image t * frame_images + first + b of `out` and, mirrored, of `out_flip` (either may be None, not both), each a
+    contiguous float32 (T * frame_images, Ho, Wo, ld) tensor of the caller's; no other image is touched.  Two views of one tensor,
+    `out_flip` starting B images in, make the input of the one-pass flip test in one launch.  Returns (out, out_flip)."""
+    return _crop_to_nhwc("clip_crop_to_nhwc_strided", frames, inv, out_hw, clip, frame_of, valid_hw, out_flip is not None, ld, border,
+                         mean, std, (frame_images, first, out, out_flip))
+
+
 def center_pool(center_xy, hw, sigma: float = 3.0, out: torch.Tensor = None, coff: int = None, clip=None, flip: bool = False,
-                device=None):
+                device=None, frame_images: int = None, first: int = 0):
     """The pooled centre map straight from the centre (``up_center_pool`` / ``up_clip_center_pool`` / ``up_clip_center_pool_flip``):
     center_xy (N, 2), or (B, T, 2) with clip = (B, T), in pixels of the hw = (H, W) map -> channel `coff` of `out`
     (N or T * B, P, Q, ld) float32 NHWC (frame-major for a clip), P = (H - 7) // 8 + 1, Q = (W - 7) // 8 + 1; no other channel is
     touched.  Without `out`: a new zero-filled (N, P, Q, 4) tensor, written at channel `coff` (default 0).  Equal bits to
-    AvgPool2d(9, 8, 1) of ``make_centermaps(center_xy, H, W, sigma)``; flip (clips only): of the mirrored maps."""
+    AvgPool2d(9, 8, 1) of ``make_centermaps(center_xy, H, W, sigma)``; flip (clips only): of the mirrored maps.  frame_images
+    (clips only, with `out`): the ``_strided`` entries — `out` is (T * frame_images, P, Q, ld) and sample (b, t) goes to image
+    t * frame_images + first + b."""
     c = _as_f64(center_xy, device if out is None else out.device)
     h, w = int(hw[0]), int(hw[1])
     p, q = (h - 7) // 8 + 1, (w - 7) // 8 + 1
@@ -2117,6 +2164,10 @@ def center_pool(center_xy, hw, sigma: float = 3.0, out: torch.Tensor = None, cof
         if tuple(c.shape) != lead + (2,):
             raise ValueError(f"center_pool: centres {tuple(c.shape)} for a clip of {lead[0]} x {lead[1]} ((B, T, 2) expected)")
     n = c.shape[0] if clip is None else lead[0] * lead[1]
+    if frame_images is not None:
+        if clip is None or out is None:
+            raise ValueError("center_pool: frame_images goes with clip=(B, T) and an `out` of T * frame_images images")
+        n = lead[1] * int(frame_images)
     if out is None:
         out = torch.zeros((n, max(p, 0), max(q, 0), 4), dtype=torch.float32, device=c.device)
         coff = 0 if coff is None else coff
@@ -2128,6 +2179,11 @@ def center_pool(center_xy, hw, sigma: float = 3.0, out: torch.Tensor = None, cof
                              f"({n}, {p}, {q}, ld) on {c.device} expected")
         if coff is None:
             raise ValueError("center_pool: `coff` names the channel of `out` to write")
+    if frame_images is not None:
+        fn = _C.lib().up_clip_center_pool_flip_strided if flip else _C.lib().up_clip_center_pool_strided
+        _C.check(fn(c.data_ptr(), float(sigma), out.data_ptr(), out.shape[3], int(coff), *lead, h, w, p, q, int(frame_images), int(first),
+                    _stream(out)), "center_pool")
+        return out
     fn = _C.lib().up_center_pool if clip is None else _C.lib().up_clip_center_pool_flip if flip else _C.lib().up_clip_center_pool
     _C.check(fn(c.data_ptr(), float(sigma), out.data_ptr(), out.shape[3], int(coff), *lead, h, w, p, q, _stream(out)), "center_pool")
     return out

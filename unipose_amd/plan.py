@@ -28,6 +28,13 @@ changing them.  Inference only.
 ``ops.set_conv_math("bf16s")`` — bf16 activations and weight images behind the fp32 stem, fp32 accumulation, fp32 maps out of the
 last convolution — again with equal bits (tests/test_plan_bf16_*.py).  Inputs, results and ``refresh`` stay fp32; the plan neither
 reads nor sets ``ops.CONV_MATH``, so plans of both storages can be alive and called in turn.
+
+``UniPosePlan(..., flip="one_pass")`` (default ``"two_pass"``; ``plan.flip_mode`` reads it back) runs the flip test of
+``flip_heatmaps``, ``final_preds(flip=True)``, ``frame_heatmaps(flip=True)`` and ``frame_final_preds(flip=True)`` as ONE trunk over
+2 * batch images, the input and its mirror: a pass less, at the workspace of a forward of twice the batch.  Its identity:
+``flip_heatmaps(x)`` has equal bits to ``ops.flip_merge(a, f, perm)`` with ``a, f`` the two halves of
+``plan2B(torch.cat([x, x.flip(3)]))``, ``plan2B`` a two-pass plan of batch 2 * batch of the same model and storage — not to the
+two-pass form, wherever a convolution picks its kernel by the number of rows.  Every other method is unchanged.
 """
 from __future__ import annotations
 
@@ -83,12 +90,16 @@ class _Plan:
     _prefix = None
     bbox = False
 
-    def _create(self, cfg, device, dtype=None):
-        """dtype: None for the plan's plain create entry, else the storage type code of its `_create_t` form"""
+    def _create(self, cfg, device, dtype=None, flip="two_pass"):
+        """dtype: None for the plan's plain create entry, else the storage type code of its `_create_t` form; flip: "two_pass" or
+        "one_pass" (UP_PLAN_FLIP_ONE_PASS through the `_create_ex` form)"""
         L = _C.lib()
-        self.cfg, self.device, self.workspace = cfg, device, None
+        self.cfg, self.device, self.workspace, self.flip_mode = cfg, device, None, flip
         self._plan = C.c_void_p()
-        if dtype is None:
+        if flip == "one_pass":
+            _C.check(getattr(L, self._prefix + "_create_ex")(C.byref(cfg), dtype or 0, _C.PLAN_FLIP_ONE_PASS, C.byref(self._plan)),
+                     self._prefix[3:] + "_create_ex")
+        elif dtype is None:
             _C.check(getattr(L, self._prefix + "_create")(C.byref(cfg), C.byref(self._plan)), self._prefix[3:] + "_create")
         else:
             _C.check(getattr(L, self._prefix + "_create_t")(C.byref(cfg), dtype, C.byref(self._plan)), self._prefix[3:] + "_create_t")
@@ -106,7 +117,8 @@ class _Plan:
         return ws.data_ptr() + off, ws.numel() - off
 
     def _flip_ws(self):
-        """the flip test keeps the first pass's heat-maps while the network runs again: a larger workspace, made at the first call"""
+        """the flip test keeps the first pass's heat-maps while the network runs again (one_pass: it runs at twice the batch): a
+        larger workspace, made at the first call"""
         return self._ws(getattr(_C.lib(), self._prefix + "_flip_workspace")(self._plan))
 
     def _out(self, who, out, shape):
@@ -129,7 +141,8 @@ class _Plan:
         return ops._perm_array(protocol.flip_perm(dataset, self.num_classes, self.bbox, pairs), self.out_channels)
 
     def _frame_ws(self, program):
-        """a program from frames keeps the mirrored input through the first trunk: its own need, made at the first call (`_flip_ws`)"""
+        """a program from frames keeps the mirrored input through the first trunk (one_pass: it is half of the one input): its own
+        need, made at the first call (`_flip_ws`)"""
         return self._ws(getattr(_C.lib(), self._prefix + "_program_workspace")(self._plan, _C.PROGRAM_FROM_FRAMES + program))
 
     def _frame_args(self, who, frames, center, scale, frame_of, rot, valid_hw, lead=None):
@@ -195,7 +208,9 @@ _STORAGE = {"f32": ("f32", 0), "fp32": ("f32", 0), "bf16": ("bf16", 1), "bf16s":
 class UniPosePlan(_Plan):
     _prefix = "up_unipose_plan"
 
-    def __init__(self, model, batch: int, height: int, width: int, storage: str = "f32"):
+    def __init__(self, model, batch: int, height: int, width: int, storage: str = "f32", flip: str = "two_pass"):
+        if not isinstance(flip, str) or flip not in ("two_pass", "one_pass"):
+            raise ValueError(f"UniPosePlan: flip {flip!r}; 'two_pass' or 'one_pass'")
         if not isinstance(storage, str) or storage not in _STORAGE:
             raise ValueError(f"UniPosePlan: storage {storage!r}; one of {sorted(_STORAGE)}")
         self.storage, dtype = _STORAGE[storage]
@@ -212,7 +227,7 @@ class UniPosePlan(_Plan):
         out_channels = model.decoder.last_conv[8].out_channels
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
         # (the default goes through up_unipose_plan_create, as before the storage option)
-        self._create(_Config(batch, height, width, os_, out_channels), w0.device, dtype if dtype else None)
+        self._create(_Config(batch, height, width, os_, out_channels), w0.device, dtype if dtype else None, flip)
         self.batch, self.height, self.width, self.out_channels = batch, height, width, out_channels
         # heat-map size: three ceil-halvings (7x7 stride-2 stem, 3x3 stride-2 max-pool, layer2's stride 2), the arithmetic of
         # plan.hip's build(): ceil(H / 8), NOT H // 8 — the two differ whenever H % 8 != 0 (a 52 x 52 input gives 7 x 7 maps)
@@ -397,10 +412,20 @@ class UniPoseLSTMPlan(_Plan):
     ``ops.set_conv_math("bf16s")`` (unipose_amd/uniposeLSTM.py): a bf16 trunk that hands over fp32 heat-maps, fp32 ConvLSTM state
     and head, their convolutions of 32-aligned input width on bf16 operands — equal bits again (tests/test_lstm_plan_bf16_*.py).
     Frames, centre maps, states, results and ``refresh`` stay float32; a ``stream_state()`` buffer has the same size in both storages.
+
+    ``UniPoseLSTMPlan(..., flip="one_pass")`` (default ``"two_pass"``; ``plan.flip_mode``) runs the flip test of
+    ``clip_flip_heatmaps``, ``clip_final_preds(flip=True)``, ``clip_frame_heatmaps(flip=True)`` and
+    ``clip_frame_final_preds(flip=True)`` as ONE pass over 2 * batch samples per frame, the clip and its mirror, each half with its own
+    recurrent state.  Its identity: ``clip_flip_heatmaps(x, cm)`` has equal bits, frame by frame, to ``ops.flip_merge`` of the two
+    batch halves of ``plan2B.clip(torch.cat([x, x.flip(-1)]), torch.cat([cm, cm.flip(-1)]))``, ``plan2B`` a two-pass plan of batch
+    2 * batch — not to the two-pass form, wherever a convolution picks its kernel by the number of rows.  Every other method, the
+    state buffer and ``plan.workspace`` of the plain methods are unchanged.
     """
     _prefix = "up_unipose_lstm_plan"
 
-    def __init__(self, model, batch: int, height: int, width: int, frames: int = 1, storage: str = "f32"):
+    def __init__(self, model, batch: int, height: int, width: int, frames: int = 1, storage: str = "f32", flip: str = "two_pass"):
+        if not isinstance(flip, str) or flip not in ("two_pass", "one_pass"):
+            raise ValueError(f"UniPoseLSTMPlan: flip {flip!r}; 'two_pass' or 'one_pass'")
         if not isinstance(storage, str) or storage not in _STORAGE:
             raise ValueError(f"UniPoseLSTMPlan: storage {storage!r}; one of {sorted(_STORAGE)}")
         self.storage, dtype = _STORAGE[storage]
@@ -416,7 +441,7 @@ class UniPoseLSTMPlan(_Plan):
         self.num_classes = K = model.num_classes
         os_ = 16 if model.wasp.aspp2.atrous_conv.dilation[0] == 18 else 8
         # (the default goes through up_unipose_lstm_plan_create, as before the storage option)
-        self._create(_LstmConfig(batch, frames, height, width, os_, K), w0.device, dtype if dtype else None)
+        self._create(_LstmConfig(batch, frames, height, width, os_, K), w0.device, dtype if dtype else None, flip)
         self.batch, self.frames, self.height, self.width = batch, frames, height, width
         self.out_channels, self.out_height, self.out_width = K + 1, (height - 1) // 8 + 1, (width - 1) // 8 + 1
         self.refresh(model)
