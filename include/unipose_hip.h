@@ -504,6 +504,33 @@ int up_lstm_bwd(const float* gates, int ldg, const float* cprev, int ldc, const 
                 const float* dcell, const float* dhide, int ldo,
                 float* dgates, float* dcprev, int64_t rows, int Cg, void* stream);
 
+/* ---- ConvLSTM state of many independent streams in one batch (no reference counterpart) ----
+ * A POOL holds the recurrent state of `slots` streams: record s starts at pool + s * slot_stride floats and is
+ * hide (rows_per_sample, ldo) then cell (rows_per_sample, ldo), fp32, rows_per_sample = h * w, ldo = rup4(K+2); slot_stride >=
+ * 2 * rows_per_sample * ldo (the plans round the record up to 256 bytes).  Every offset is computed in 64 bits.
+ * A call works on B samples of rows_per_sample consecutive rows each and takes a per-call table on the HOST, read before the call
+ * returns and passed to the kernel by value: slot_host[b] the record of sample b, or -1 for an idle lane; first_host[b] != 0 for a
+ * sample that starts (or restarts).  A first and an idle sample are both computed as a first frame (LSTM_0); nothing of the pool is
+ * read for them and nothing is written for an idle one.
+ * UP_ERR_INVALID (nothing launched, nothing written): B outside 1 .. UP_SERVE_CAP, slots < 1, a slot outside -1 .. slots-1, the same
+ * slot >= 0 twice, a null pointer, a size <= 0, a stride smaller than the rows it strides.
+ *   up_lstm_state_gather  writes all ldo lanes dst[row * ldd + coff .. + ldo) of every row: the pool's hide row of slot[b] for a
+ *                         continuing sample, +0.0f for a first or idle one.  No other lane of dst is touched.
+ *   up_lstm_serve_fwd     one element per (row, lane < ldo).  Lanes < Cg: a first or idle sample evaluates up_lstm0_fwd's formula
+ *                         on gates0 [rows][ldg0] (g|i|o), a continuing one up_lstm_fwd's on gates [rows][ldg] (g|i|o|f) with the
+ *                         previous cell read in place from its record; the result goes to cell / hide [rows][ldo] (lanes < Cg
+ *                         only, as up_lstm_fwd) and, for slot >= 0, into the record, by the thread that read it.  Lanes Cg .. ldo-1
+ *                         are written as +0.0f into the record only, so a fresh pool may be uninitialised memory and the next gather
+ *                         copies whole padded rows.  gates0 may be NULL when no sample is first or idle, gates when none
+ *                         continues; a NULL one that a sample needs is UP_ERR_INVALID.
+ * Each sample's rows equal, bit for bit, up_lstm0_fwd resp. up_lstm_fwd on those rows (the same device functions). */
+enum { UP_SERVE_CAP = 64 };
+int up_lstm_state_gather(const float* pool, int64_t slot_stride, int slots, const int32_t* slot_host, const int32_t* first_host, int B,
+                         int64_t rows_per_sample, int ldo, float* dst, int ldd, int coff, void* stream);
+int up_lstm_serve_fwd(const float* gates0, int ldg0, const float* gates, int ldg, float* pool, int64_t slot_stride, int slots,
+                      const int32_t* slot_host, const int32_t* first_host, float* cell, float* hide, int ldo, int B,
+                      int64_t rows_per_sample, int Cg, void* stream);
+
 /* ---- heat-map argmax (utils/evaluate.py:32-54 get_max_preds; utils/utils.py:94-106) ----
  * hm: NCHW fp32 (B,J,H,W) as returned by the model.  One wavefront per (b,j): first-max flat index
  * (lowest index wins ties), preds = (idx % W, idx / W) zeroed where max <= 0.  idx may be NULL. */
@@ -1036,6 +1063,44 @@ int up_unipose_lstm_stream_frame_final_preds(up_unipose_lstm_plan* plan, const v
                                              float mean, float stdv, const double* center_xy, double sigma, void* state, int first,
                                              const double* inv, int res0, int res1, float* preds_xy, float* coords_xy, float* maxvals,
                                              float* heat_nchw, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Many independent streams in ONE call (ABI 10 additions).  The stream entries above take one `first` flag and one state buffer for
+ * the whole batch, so their B samples must start together and never restart.  The two entries below are those entries for a batch
+ * whose samples are in different phases: the state lives in a caller-owned POOL of `slots` per-stream records (layout and tables:
+ * up_lstm_state_gather / up_lstm_serve_fwd above; here rows_per_sample = h * w, ldo = rup4(K+2), the record stride rounded up to 256
+ * bytes; the pool is up_unipose_lstm_plan_pool_bytes(plan, slots) bytes, 256-byte aligned, and may start as uninitialised memory),
+ * and each call names, per sample b of the plan's batch, slot_host[b] (the record of its stream, or -1 for an idle lane) and
+ * first_host[b] (!= 0: the stream starts or restarts with this frame).  Both tables are host memory, read before the call returns.
+ *   up_unipose_lstm_serve_keypoints          up_unipose_lstm_stream_keypoints: x_nchw, center_nchw, the grid and the outputs as there.
+ *   up_unipose_lstm_serve_frame_final_preds  up_unipose_lstm_stream_frame_final_preds: the crop, centre and way-back arguments as there.
+ * THE RESULT, by definition: lane b of a call (its preds_xy / maxvals / idx / coords_xy / heat_nchw rows) equals, bit for bit, lane b
+ * of this plan's own stream entry at the same batch on the same inputs — called with first != 0 for a first or idle lane; for a
+ * continuing lane with first == 0 and a state buffer that holds that stream's state in lane b (the other lanes anything finite, e.g.
+ * zeros).  The record of slot_host[b] >= 0 after the call equals lane b of the state buffer after that stream call: hide rows, then
+ * cell rows, the pad lanes +0.0f.  Records of slots the table does not name keep every byte; for an idle lane nothing is written.
+ * It is lane b, not any lane: a convolution's tail-tile K-split makes a row's summation order depend on its position in the batch, so
+ * the same stream served in another lane may differ in the last bits (as it does between two batch sizes).
+ * The launches: the trunk, hand-over and centre pooling of the stream programs, then BOTH gate convolutions at the plan's batch (the
+ * lstm_0 one skipped when no sample is first or idle; the copy of z, the gather and the lstm one skipped when none continues), one
+ * up_lstm_state_gather straight into the gate convolution's input, one up_lstm_serve_fwd, the head and the ending.  No flip test
+ * inside a stream; UP_PLAN_FLIP_ONE_PASS changes nothing here.  Both storages.
+ * Workspace: up_unipose_lstm_plan_program_workspace(plan, UP_PROGRAM_SERVE + 0) for _serve_keypoints, + 1 for
+ * _serve_frame_final_preds (0 for any other k); no other figure of the plan changes.
+ * Refused before anything is launched, outputs and pool untouched: a plan of batch > UP_SERVE_CAP (UP_ERR_UNSUPPORTED, from these
+ * entries only), a NULL or misaligned pool, slots < 1, a slot outside -1 .. slots-1, the same slot >= 0 twice, NULL tables, and
+ * everything the stream entry refuses (unset weights, a too-small workspace: UP_ERR_WORKSPACE). */
+enum { UP_PROGRAM_SERVE = 512 };
+size_t up_unipose_lstm_plan_pool_bytes(const up_unipose_lstm_plan* plan, int slots);   /* 0 for NULL or slots < 1 */
+int up_unipose_lstm_serve_keypoints(up_unipose_lstm_plan* plan, const float* x_nchw, const float* center_nchw, void* pool, int slots,
+                                    const int32_t* slot_host, const int32_t* first_host, int out_h, int out_w, int32_t* idx,
+                                    float* preds_xy, float* maxvals, float* heat_nchw, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int up_unipose_lstm_serve_frame_final_preds(up_unipose_lstm_plan* plan, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                            const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv, float border,
+                                            float mean, float stdv, const double* center_xy, double sigma, void* pool, int slots,
+                                            const int32_t* slot_host, const int32_t* first_host, const double* inv, int res0, int res1,
+                                            float* preds_xy, float* coords_xy, float* maxvals, float* heat_nchw, void* workspace,
+                                            size_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg; no reference counterpart) ----
  * Between begin/end every MFMA convolution launch is bracketed by two hipEvents on its stream;

@@ -223,6 +223,14 @@ SIGNATURES = {
     "up_unipose_plan_flags": (_i, [_p]),
     "up_unipose_lstm_plan_create_ex": (_i, [_p, _i, _i, C.POINTER(_p)]),
     "up_unipose_lstm_plan_flags": (_i, [_p]),
+    "up_lstm_state_gather": (_i, [_p, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i64, _i, _p, _i, _i, _p]),
+    "up_lstm_serve_fwd": (_i, [_p, _i, _p, _i, _p, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _p, _i, _i, _i64, _i, _p]),
+    "up_unipose_lstm_plan_pool_bytes": (_sz, [_p, _i]),
+    "up_unipose_lstm_serve_keypoints": (_i, [_p, _p, _p, _p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _p, _p, _p, _p, _p,
+                                             _sz, _p]),
+    "up_unipose_lstm_serve_frame_final_preds": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _f, _f, _p, C.c_double, _p, _i,
+                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i, _i, _p, _p, _p, _p, _p, _sz,
+                                                     _p]),
     "up_profile_variants": (_i, []),
     "up_profile_variant_name": (C.c_char_p, [_i]),
     "up_profile_begin": (_i, []),
@@ -234,6 +242,7 @@ SIGNATURES = {
 # UP_PROGRAM_FROM_FRAMES: up_unipose_plan_program_workspace(plan, 256 + k), k = 0, 4, 5, 6;
 # up_unipose_lstm_plan_program_workspace(plan, 256 + k), k = 2, 4, 5, 6, 7, 8
 PROGRAM_FROM_FRAMES = 256
+PROGRAM_SERVE = 512             # UP_PROGRAM_SERVE: up_unipose_lstm_plan_program_workspace(plan, 512 + k), k = 0 (serve), 1 (serve_frames)
 PLAN_FLIP_ONE_PASS = 1          # UP_PLAN_FLIP_ONE_PASS: flags of up_unipose_plan_create_ex / up_unipose_lstm_plan_create_ex
 
 _lib = None

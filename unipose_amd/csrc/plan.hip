@@ -80,12 +80,15 @@ struct Conv {
     float* w_fwd = nullptr;   // the plan's store of that name (Weights::bind): the fp32 image, or the bf16 hi plane
     float* bias = nullptr;
 };
-// one Kind per C function called (STATE_IN / STATE_OUT: up_copy2d from / to the caller's state buffer)
+// one Kind per C function called (STATE_IN / STATE_OUT: up_copy2d from / to the caller's state buffer; GATHER / SERVE:
+// up_lstm_state_gather / up_lstm_serve_fwd on the caller's state pool)
 enum Kind {
     TO_NHWC, CONV, MAXPOOL, BILINEAR, GAP, COPY, ZERO, TO_NCHW, DECODE, PERSONS, TO_NHWC_FLIP, MERGE, FINAL, CROP,
     POOL, LSTM0, LSTM, CLIP_TO_NHWC, CLIP_TO_NCHW, CLIP_POOL, CLIP_TO_NHWC_FLIP, CLIP_POOL_FLIP, CLIP_DECODE, CLIP_FINAL,
-    STATE_IN, STATE_OUT, CLIP_CROP, CENTER_POOL, CLIP_CENTER_POOL, CLIP_CENTER_POOL_FLIP, CLIP_MERGE
+    STATE_IN, STATE_OUT, CLIP_CROP, CENTER_POOL, CLIP_CENTER_POOL, CLIP_CENTER_POOL_FLIP, CLIP_MERGE, GATHER, SERVE
 };
+enum When { ALWAYS, ANY_FIRST, ANY_NEXT };   // a serving call: launched whatever its table says, or only where a sample is first or
+                                             // idle, or only where one continues
 enum Ext { X, CENTER, PREV_HIDE, PREV_CELL, HEAT, CELL, HIDE };   // caller-owned tensors of a call
 // Sizes, strides and physical channel counts come from the tensors an op names; the fields below are what they do not hold.
 struct Op {
@@ -103,6 +106,7 @@ struct Op {
     int lds = 0, ldd = 0;      // COPY: row strides of source and destination, in elements
     int64_t rows = 0;          // COPY: rows of `ch` elements
     int half = 0;              // STATE_IN / STATE_OUT: 0 the hidden state, 1 the cell state of the caller's buffer
+    When when = ALWAYS;        // the serving programs: skipped at run time where no sample of the call needs it
 };
 
 struct Plan {
@@ -380,7 +384,8 @@ enum Ending {
     END_FINAL          // up_final_preds straight from the NHWC maps
 };
 enum Counts { COUNTS_OWN, COUNTS_PLAIN, COUNTS_FLIP };    // toward neither figure, workspace() or flip_workspace()
-enum State { STATE_NONE, STATE_NCHW, STATE_BUFFER };      // the recurrent state: none, the caller's NCHW tensors, its opaque NHWC buffer
+// the recurrent state: none, the caller's NCHW tensors, its opaque NHWC buffer, its pool of per-stream records
+enum State { STATE_NONE, STATE_NCHW, STATE_BUFFER, STATE_POOL };
 struct Program {
     int number;        // as up_*_plan_program_workspace() takes it
     Input input;
@@ -416,6 +421,13 @@ static const Program IMAGE_PROGRAMS[] = {
 // state; the clip programs its whole-clip unroll (_unroll_clip: batch_frames = batch_head = True), the flip test running the
 // whole clip twice, each pass with its own recurrent state, so a flip program returns none.  The stream programs are the step
 // programs with the state in the caller's buffer and up_heatmap_decode at the end; their NCHW heat-maps are optional.
+// The serving programs (UP_PROGRAM_SERVE + 0 / + 1) are the stream programs for a batch whose samples are in different phases: BOTH
+// gate convolutions at the plan's batch, the previous hidden state gathered per sample from the caller's pool straight into `zh`
+// (up_lstm_state_gather, in place of STATE_IN and the copy behind it), ONE up_lstm_serve_fwd that picks the formula per sample and
+// keeps the pool (in place of the two gate kernels, STATE_IN of the cell and both STATE_OUT).  At run time the lstm_0 convolution is
+// skipped where no sample is first or idle; the copy of z, the gather and the lstm convolution where none continues.  A 3x3
+// convolution mixes no images and a row's summation order depends on its position only, so lane b equals lane b of the stream
+// program of its phase.  UP_PLAN_FLIP_ONE_PASS leaves them as they are.
 // From frames (the rows numbered UP_PROGRAM_FROM_FRAMES + k, k the program the row otherwise equals): ONE crop launch stands in place
 // of the layout pass(es) and, in the flip rows, fills the mirrored input too, which then stays alive through the first pass; the
 // pooled centre map comes straight from the centre coordinates (up_center_pool and its clip forms), in the mirrored pass from the
@@ -436,6 +448,8 @@ static const Program LSTM_PROGRAMS[] = {
     {UP_PROGRAM_FROM_FRAMES + 6, IN_CLIP_FRAMES, false, END_FINAL, COUNTS_OWN},
     {UP_PROGRAM_FROM_FRAMES + 7, IN_FRAMES, false, END_FINAL, COUNTS_OWN, STATE_NONE, STATE_BUFFER},     // up_unipose_lstm_stream_frame_final_preds
     {UP_PROGRAM_FROM_FRAMES + 8, IN_FRAMES, false, END_FINAL, COUNTS_OWN, STATE_BUFFER, STATE_BUFFER},
+    {UP_PROGRAM_SERVE + 0, IN_NCHW, false, END_DECODE, COUNTS_OWN, STATE_POOL, STATE_POOL},     // up_unipose_lstm_serve_keypoints
+    {UP_PROGRAM_SERVE + 1, IN_FRAMES, false, END_FINAL, COUNTS_OWN, STATE_POOL, STATE_POOL},    // up_unipose_lstm_serve_frame_final_preds
 };
 template <size_t N>
 static int find(const Program (&table)[N], Input input, bool flip, Ending end, State from = STATE_NONE) {
@@ -637,7 +651,23 @@ static LstmPass lstm_pass(Plan& p, const up_unipose_lstm_config& c, const Progra
         Op op;
         op.n = B; op.ch = cg;
         op.out = ct; op.res = ht;
-        if (t == 0 && g.from == STATE_NONE) {    // LSTM_0 (uniposeLSTM.py:9-24)
+        if (g.from == STATE_POOL) {              // both gate convolutions, each sample's formula picked by the call's table
+            op.kind = SERVE;
+            op.in = p.conv("lstm_0", zt, B, h, w, ldz, cg, 3 * cg, 3, 1, 1, 1, 0, true);
+            p.ops.back().when = ANY_FIRST;
+            Ref zh;
+            zh.id = p.tensor(B, h, w, ldz + ldo);
+            p.copy(zt, ldz, zh, ldz + ldo, 0, (int64_t)frame, ldz);
+            p.ops.back().when = ANY_NEXT;
+            Op in;
+            in.kind = GATHER;
+            in.out = zh; in.coff = ldz;
+            in.n = B;
+            in.when = ANY_NEXT;
+            p.push(in);
+            op.aux = p.conv("lstm", zh, B, h, w, ldz + ldo, ldz + ldo, 4 * cg, 3, 1, 1, 1, 0, true);
+            p.ops.back().when = ANY_NEXT;
+        } else if (t == 0 && g.from == STATE_NONE) {    // LSTM_0 (uniposeLSTM.py:9-24)
             op.kind = LSTM0;
             op.in = p.conv("lstm_0", zt, B, h, w, ldz, cg, 3 * cg, 3, 1, 1, 1, 0, true);
         } else {                              // LSTM (uniposeLSTM.py:27-64): ONE convolution over cat(z, prev_hide)
@@ -725,20 +755,22 @@ static void build_lstm(Plan& p, const up_unipose_lstm_config& c, const Program& 
     Ref cl = a.cells, hl = a.hides;            // the state of the last frame
     cl.elems += (T - 1) * frame * ldo;
     hl.elems += (T - 1) * frame * ldo;
-    if (g.to == STATE_BUFFER) {                // the new state into the caller's buffer, then the joints
-        op = Op();
-        op.kind = STATE_OUT;
-        op.in = hl; op.half = 0;
-        p.push(op);
-        op.in = cl; op.half = 1;
-        p.push(op);
+    if (g.to == STATE_BUFFER || g.to == STATE_POOL) {      // the new state into the caller's buffer (SERVE has kept the pool), then the joints
+        if (g.to == STATE_BUFFER) {
+            op = Op();
+            op.kind = STATE_OUT;
+            op.in = hl; op.half = 0;
+            p.push(op);
+            op.in = cl; op.half = 1;
+            p.push(op);
+        }
         op = Op();
         op.kind = g.end == END_FINAL ? FINAL : DECODE;
         op.in = a.y;
         op.n = B; op.ch = hc;
         p.push(op);
     }
-    if (g.end == END_HEAT || g.to == STATE_BUFFER) {
+    if (g.end == END_HEAT || g.to == STATE_BUFFER || g.to == STATE_POOL) {
         op = Op();
         op.kind = clip ? CLIP_TO_NCHW : TO_NCHW;     // TO_NCHW is skipped where the caller passes no tensor (a stream's heat)
         op.in = a.y;
@@ -781,6 +813,11 @@ struct Io {
     float* coords = nullptr;
     float* state = nullptr;          // STATE_IN / STATE_OUT: the caller's buffer, hide then cell, state_half elements each
     size_t state_half = 0;
+    float* pool = nullptr;           // GATHER / SERVE: the caller's pool (record stride in floats), its tables (host), and how many
+    int64_t slot_stride = 0;         // of the samples are first or idle resp. continue (what the ops with a `when` are skipped by)
+    int slots = 0, firsts = 0, nexts = 0;
+    const int32_t* slot_host = nullptr;
+    const int32_t* first_host = nullptr;
     const void* src = nullptr;       // CROP: the arguments of up_crop_to_nhwc
     int src_type = 0, frames = 0, src_h = 0, src_w = 0;
     const int32_t* frame_of = nullptr;
@@ -805,6 +842,7 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
         const Tensor& o = op.out.id < 0 ? none : p.tensors[op.out.id];
         const int64_t image = (int64_t)i.h * i.w * i.c;
         int e = UP_OK;
+        if ((op.when == ANY_FIRST && !io.firsts) || (op.when == ANY_NEXT && !io.nexts)) continue;
         switch (op.kind) {
         case TO_NHWC:
             e = up_nchw_to_nhwc(io.in(op.ext), ptr(op.out), op.n, op.ch, o.h, o.w, o.c, stream);
@@ -955,6 +993,15 @@ static int run(const Plan& p, const Io& io, unsigned char* ws, void* stream, con
             break;
         case STATE_OUT:
             e = up_copy2d(ptr(op.in), i.c, io.state + op.half * io.state_half, i.c, (int64_t)i.n * i.h * i.w, i.c, stream);
+            break;
+        case GATHER:                           // the hidden states into the lanes of `zh` behind z: all o.c - coff of them
+            e = up_lstm_state_gather(io.pool, io.slot_stride, io.slots, io.slot_host, io.first_host, op.n, (int64_t)o.h * o.w,
+                                     o.c - op.coff, ptr(op.out), o.c, op.coff, stream);
+            break;
+        case SERVE:                            // a gate tensor whose convolution was skipped is not passed
+            e = up_lstm_serve_fwd(io.firsts ? ptr(op.in) : nullptr, i.c, io.nexts ? ptr(op.aux) : nullptr, p.tensors[op.aux.id].c, io.pool,
+                                  io.slot_stride, io.slots, io.slot_host, io.first_host, ptr(op.out), ptr(op.res), o.c, op.n,
+                                  (int64_t)i.h * i.w, op.ch, stream);
             break;
         }
         if (e) return e;
@@ -1501,6 +1548,16 @@ extern "C" size_t up_unipose_lstm_plan_state_bytes(const up_unipose_lstm_plan* p
     return pl ? 2 * pl->state_half * sizeof(float) : 0;
 }
 
+// one record of a state pool in floats: hide then cell, (h, w, rup4(K + 2)) each, the stride rounded up to 256 bytes
+static size_t pool_record(const up_unipose_lstm_plan* pl) {
+    const size_t h = (pl->cfg.height - 1) / 8 + 1, w = (pl->cfg.width - 1) / 8 + 1, ldo = plan::rup4(pl->cfg.num_classes + 2);
+    return (2 * h * w * ldo + 63) / 64 * 64;
+}
+
+extern "C" size_t up_unipose_lstm_plan_pool_bytes(const up_unipose_lstm_plan* pl, int slots) {
+    return pl && slots >= 1 ? (size_t)slots * pool_record(pl) * sizeof(float) : 0;
+}
+
 // The program of an entry's arguments, ready and run: a too-small workspace is UP_ERR_WORKSPACE from this plan.  whole: step and clip
 // ask for up_unipose_lstm_plan_workspace() (as ever), the evaluation entries for their program's own need.
 static int launch(up_unipose_lstm_plan* pl, plan::Input input, bool flip, plan::Ending end, plan::State from, bool whole, const plan::Io& io,
@@ -1701,4 +1758,65 @@ extern "C" int up_unipose_lstm_stream_frame_final_preds(up_unipose_lstm_plan* pl
     io.heat = heat_nchw;
     return launch(pl, plan::IN_FRAMES, false, plan::END_FINAL, first ? plan::STATE_NONE : plan::STATE_BUFFER, false, io, workspace, ws_bytes,
                   stream, "unipose_lstm_stream_frame_final_preds");
+}
+
+// ---- many streams in one call: the state in a pool of per-stream records ----------------------------------------------------------------
+// What both serving entries check of the pool and the table, before anything is launched, and the Io fields of GATHER / SERVE.
+static int serve_io(up_unipose_lstm_plan* pl, plan::Io& io, void* pool, int slots, const int32_t* slot_host, const int32_t* first_host,
+                    const char* what) {
+    UP_REQUIRE(pl->cfg.batch <= UP_SERVE_CAP, UP_ERR_UNSUPPORTED, "%s: a plan of batch %d (the table holds up to %d samples)", what,
+               pl->cfg.batch, (int)UP_SERVE_CAP);
+    UP_REQUIRE(pool && (reinterpret_cast<uintptr_t>(pool) & 255) == 0, UP_ERR_INVALID,
+               "%s: a 256-byte aligned pool of up_unipose_lstm_plan_pool_bytes(plan, slots) bytes is needed", what);
+    if (int e = serve_table_check(what, slots, slot_host, first_host, pl->cfg.batch, &io.firsts, &io.nexts)) return e;
+    io.pool = static_cast<float*>(pool);
+    io.slot_stride = (int64_t)pool_record(pl);
+    io.slots = slots;
+    io.slot_host = slot_host;
+    io.first_host = first_host;
+    return UP_OK;
+}
+
+extern "C" int up_unipose_lstm_serve_keypoints(up_unipose_lstm_plan* pl, const float* x_nchw, const float* center_nchw, void* pool, int slots,
+                                               const int32_t* slot_host, const int32_t* first_host, int out_h, int out_w, int32_t* idx,
+                                               float* preds_xy, float* maxvals, float* heat_nchw, void* workspace, size_t ws_bytes,
+                                               void* stream) {
+    UP_REQUIRE(pl && x_nchw && center_nchw && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_serve_keypoints: null argument");
+    plan::Io io;
+    if (int e = serve_io(pl, io, pool, slots, slot_host, first_host, "unipose_lstm_serve_keypoints")) return e;
+    if (int e = plan::grid_ok(out_h, out_w, pl->cfg.height, pl->cfg.width, "unipose_lstm_serve_keypoints")) return e;
+    io.x = x_nchw;
+    io.center = center_nchw;
+    io.dec_h = out_h;
+    io.dec_w = out_w;
+    io.idx = idx;
+    io.preds = preds_xy;
+    io.maxvals = maxvals;
+    io.heat = heat_nchw;
+    return launch(pl, plan::IN_NCHW, false, plan::END_DECODE, plan::STATE_POOL, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_serve_keypoints");
+}
+
+extern "C" int up_unipose_lstm_serve_frame_final_preds(up_unipose_lstm_plan* pl, const void* src_hwc, int src_type, int F, int Hs, int Ws,
+                                                       const int32_t* frame_of, const int32_t* valid_hw, const double* crop_inv,
+                                                       float border, float mean, float stdv, const double* center_xy, double sigma,
+                                                       void* pool, int slots, const int32_t* slot_host, const int32_t* first_host,
+                                                       const double* inv, int res0, int res1, float* preds_xy, float* coords_xy,
+                                                       float* maxvals, float* heat_nchw, void* workspace, size_t ws_bytes, void* stream) {
+    UP_REQUIRE(pl && preds_xy && maxvals && workspace, UP_ERR_INVALID, "unipose_lstm_serve_frame_final_preds: null argument");
+    UP_REQUIRE(res0 > 0 && res1 > 0, UP_ERR_INVALID, "unipose_lstm_serve_frame_final_preds: res %d, %d", res0, res1);
+    plan::Io io;
+    if (int e = serve_io(pl, io, pool, slots, slot_host, first_host, "unipose_lstm_serve_frame_final_preds")) return e;
+    if (int e = lstm_frame_io(pl->cfg.batch, io, src_hwc, src_type, F, Hs, Ws, frame_of, valid_hw, crop_inv, border, mean, stdv, center_xy,
+                              sigma, "unipose_lstm_serve_frame_final_preds"))
+        return e;
+    io.inv = inv;
+    io.res0 = res0;
+    io.res1 = res1;
+    io.preds = preds_xy;
+    io.coords = coords_xy;
+    io.maxvals = maxvals;
+    io.heat = heat_nchw;
+    return launch(pl, plan::IN_FRAMES, false, plan::END_FINAL, plan::STATE_POOL, false, io, workspace, ws_bytes, stream,
+                  "unipose_lstm_serve_frame_final_preds");
 }

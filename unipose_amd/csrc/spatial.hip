@@ -448,17 +448,30 @@ __global__ void __launch_bounds__(256) clip_avgpool9s8_strided_kernel(const floa
 
 // ---- ConvLSTM gates -------------------------------------------------------------------------
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
+// The two cell formulas, channel c of one row `g` of stacked gate pre-activations (g | i | o (| f), each Cg wide): shared by the
+// plain forward kernels and lstm_serve_fwd_kernel, so a sample computes the same bits through either.
+// LSTM_0 (uniposeLSTM.py:9-24) ...
+__device__ __forceinline__ void lstm0_at(const float* g, int Cg, int c, float& cl, float& hd) {
+    float gg = tanhf(g[c]), ii = sigm(g[Cg + c]), oo = sigm(g[2 * Cg + c]);
+    cl = tanhf(gg * ii);
+    hd = oo * cl;
+}
+// ... and LSTM (uniposeLSTM.py:27-64) with the previous cell value cp
+__device__ __forceinline__ void lstm_at(const float* g, int Cg, int c, float cp, float& cl, float& hd) {
+    float gg = tanhf(g[c]), ii = sigm(g[Cg + c]), oo = sigm(g[2 * Cg + c]), ff = sigm(g[3 * Cg + c]);
+    cl = ff * cp + ii * gg;
+    hd = oo * tanhf(cl);
+}
 
 __global__ void __launch_bounds__(256) lstm0_fwd_kernel(const float* G, int ldg, float* cell, float* hide, int ldo,
                                                         int64_t total, int Cg) {
     UP_GRID_STRIDE(i, total) {
         int64_t r = i / Cg;
         int c = (int)(i - r * Cg);
-        const float* g = G + r * ldg;
-        float gg = tanhf(g[c]), ii = sigm(g[Cg + c]), oo = sigm(g[2 * Cg + c]);
-        float cl = tanhf(gg * ii);
+        float cl, hd;
+        lstm0_at(G + r * ldg, Cg, c, cl, hd);
         cell[r * ldo + c] = cl;
-        hide[r * ldo + c] = oo * cl;
+        hide[r * ldo + c] = hd;
     }
 }
 __global__ void __launch_bounds__(256) lstm0_bwd_kernel(const float* G, int ldg, const float* dcell,
@@ -484,11 +497,10 @@ __global__ void __launch_bounds__(256) lstm_fwd_kernel(const float* G, int ldg, 
     UP_GRID_STRIDE(i, total) {
         int64_t r = i / Cg;
         int c = (int)(i - r * Cg);
-        const float* g = G + r * ldg;
-        float gg = tanhf(g[c]), ii = sigm(g[Cg + c]), oo = sigm(g[2 * Cg + c]), ff = sigm(g[3 * Cg + c]);
-        float cl = ff * cprev[r * ldc + c] + ii * gg;
+        float cl, hd;
+        lstm_at(G + r * ldg, Cg, c, cprev[r * ldc + c], cl, hd);
         cell[r * ldo + c] = cl;
-        hide[r * ldo + c] = oo * tanhf(cl);
+        hide[r * ldo + c] = hd;
     }
 }
 __global__ void __launch_bounds__(256) lstm_bwd_kernel(const float* G, int ldg, const float* cprev, int ldc,
@@ -508,6 +520,51 @@ __global__ void __launch_bounds__(256) lstm_bwd_kernel(const float* G, int ldg, 
         o[2 * Cg + c] = dh * tc * oo * (1.f - oo);
         o[3 * Cg + c] = dc * cprev[r * ldc + c] * ff * (1.f - ff);
         dcprev[r * ldo + c] = dc * ff;
+    }
+}
+
+// ---- ConvLSTM state of many streams in one batch (include/unipose_hip.h) ---------------------------------------------
+// The per-call table travels by value, like FlipPerm: 264 bytes of kernel arguments.  A sample whose bit is set in `first` (a first
+// or an idle one) is computed as a first frame and reads nothing of the pool; slot < 0 (idle) writes nothing of it either.
+struct ServeTable {
+    int32_t slot[UP_SERVE_CAP];
+    uint64_t first;
+};
+// One thread per (row, lane < ldo), lanes fastest.  Record of slot s: hide (rps, ldo) then cell (rps, ldo) at pool + s * stride.
+__global__ void __launch_bounds__(256) lstm_state_gather_kernel(const float* pool, int64_t stride, ServeTable tab, int64_t rps, int ldo,
+                                                                float* dst, int ldd, int coff, int64_t total) {
+    UP_GRID_STRIDE(i, total) {
+        const int64_t row = i / ldo;
+        const int c = (int)(i - row * ldo);
+        const int b = (int)(row / rps);
+        const int64_t rl = row - b * rps;
+        const bool first = (tab.first >> b) & 1;
+        dst[row * ldd + coff + c] = first ? 0.0f : pool[(int64_t)tab.slot[b] * stride + rl * ldo + c];
+    }
+}
+__global__ void __launch_bounds__(256) lstm_serve_fwd_kernel(const float* G0, int ldg0, const float* G, int ldg, float* pool,
+                                                             int64_t stride, ServeTable tab, float* cell, float* hide, int ldo,
+                                                             int64_t rps, int64_t total, int Cg) {
+    UP_GRID_STRIDE(i, total) {
+        const int64_t row = i / ldo;
+        const int c = (int)(i - row * ldo);
+        const int b = (int)(row / rps);
+        const int64_t rl = row - b * rps;
+        const int slot = tab.slot[b];
+        const bool first = (tab.first >> b) & 1;
+        float* rec_hide = pool + (int64_t)(slot < 0 ? 0 : slot) * stride + rl * ldo + c;     // (not touched for slot < 0)
+        float* rec_cell = rec_hide + rps * ldo;
+        float cl = 0.0f, hd = 0.0f;
+        if (c < Cg) {
+            if (first) lstm0_at(G0 + row * ldg0, Cg, c, cl, hd);
+            else lstm_at(G + row * ldg, Cg, c, *rec_cell, cl, hd);
+            cell[row * ldo + c] = cl;
+            hide[row * ldo + c] = hd;
+        }
+        if (slot >= 0) {
+            *rec_hide = hd;
+            *rec_cell = cl;
+        }
     }
 }
 
@@ -1648,6 +1705,50 @@ extern "C" int up_lstm_bwd(const float* gates, int ldg, const float* cprev, int 
     UP_LAUNCH_1D(lstm_bwd_kernel, total, as_stream(stream), gates, ldg, cprev, ldc, cell, dcell, dhide, ldo, dgates,
                  dcprev, total, Cg);
     return check_launch("lstm_bwd");
+}
+
+// the host tables of a serving call, checked, as the kernel argument
+static int serve_table(const char* what, int slots, const int32_t* slot_host, const int32_t* first_host, int B, ServeTable& tab,
+                       int& firsts, int& conts) {
+    if (int e = serve_table_check(what, slots, slot_host, first_host, B, &firsts, &conts)) return e;
+    memset(&tab, 0, sizeof(tab));
+    for (int b = 0; b < B; ++b) {
+        tab.slot[b] = slot_host[b];
+        if (slot_host[b] < 0 || first_host[b] != 0) tab.first |= 1ull << b;
+    }
+    return UP_OK;
+}
+extern "C" int up_lstm_state_gather(const float* pool, int64_t slot_stride, int slots, const int32_t* slot_host, const int32_t* first_host,
+                                    int B, int64_t rows_per_sample, int ldo, float* dst, int ldd, int coff, void* stream) {
+    ServeTable tab;
+    int firsts = 0, conts = 0;
+    if (int e = serve_table("lstm_state_gather", slots, slot_host, first_host, B, tab, firsts, conts)) return e;
+    UP_REQUIRE(pool && dst && rows_per_sample > 0 && ldo > 0 && coff >= 0 && (int64_t)coff + ldo <= ldd &&
+                   rows_per_sample <= INT64_MAX / (2 * UP_SERVE_CAP) / ldo && slot_stride >= 2 * rows_per_sample * ldo,
+               UP_ERR_INVALID, "lstm_state_gather: bad argument (%lld rows of %d lanes, record stride %lld, lanes %d.. of %d)",
+               (long long)rows_per_sample, ldo, (long long)slot_stride, coff, ldd);
+    const int64_t total = (int64_t)B * rows_per_sample * ldo;
+    UP_LAUNCH_1D(lstm_state_gather_kernel, total, as_stream(stream), pool, slot_stride, tab, rows_per_sample, ldo, dst, ldd, coff, total);
+    return check_launch("lstm_state_gather");
+}
+extern "C" int up_lstm_serve_fwd(const float* gates0, int ldg0, const float* gates, int ldg, float* pool, int64_t slot_stride, int slots,
+                                 const int32_t* slot_host, const int32_t* first_host, float* cell, float* hide, int ldo, int B,
+                                 int64_t rows_per_sample, int Cg, void* stream) {
+    ServeTable tab;
+    int firsts = 0, conts = 0;
+    if (int e = serve_table("lstm_serve_fwd", slots, slot_host, first_host, B, tab, firsts, conts)) return e;
+    UP_REQUIRE(pool && cell && hide && rows_per_sample > 0 && Cg > 0 && ldo >= Cg && rows_per_sample <= INT64_MAX / (2 * UP_SERVE_CAP) / ldo &&
+                   slot_stride >= 2 * rows_per_sample * ldo,
+               UP_ERR_INVALID, "lstm_serve_fwd: bad argument (%lld rows of %d lanes, %d gate channels, record stride %lld)",
+               (long long)rows_per_sample, ldo, Cg, (long long)slot_stride);
+    UP_REQUIRE(!firsts || (gates0 && ldg0 >= 3 * Cg), UP_ERR_INVALID,
+               "lstm_serve_fwd: %d first or idle samples need gates0 (row stride %d >= %d)", firsts, ldg0, 3 * Cg);
+    UP_REQUIRE(!conts || (gates && ldg >= 4 * Cg), UP_ERR_INVALID, "lstm_serve_fwd: %d continuing samples need gates (row stride %d >= %d)",
+               conts, ldg, 4 * Cg);
+    const int64_t total = (int64_t)B * rows_per_sample * ldo;
+    UP_LAUNCH_1D(lstm_serve_fwd_kernel, total, as_stream(stream), gates0, ldg0, gates, ldg, pool, slot_stride, tab, cell, hide, ldo,
+                 rows_per_sample, total, Cg);
+    return check_launch("lstm_serve_fwd");
 }
 
 extern "C" int up_heatmap_argmax(const float* hm, int B, int J, int H, int W, int32_t* idx, float* preds_xy,

@@ -60,6 +60,28 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// The per-call table of the stream-serving entries (up_lstm_state_gather, up_lstm_serve_fwd, up_unipose_lstm_serve_*): B samples,
+// slot_host[b] the pool record of sample b or -1 (an idle lane), first_host[b] != 0 a sample that starts.  Refused: B outside
+// 1 .. UP_SERVE_CAP, a slot outside -1 .. slots-1, a slot >= 0 named twice.  firsts / conts: the samples computed as a first frame
+// (first or idle) and the continuing ones.
+static inline int serve_table_check(const char* what, int slots, const int32_t* slot_host, const int32_t* first_host, int B, int* firsts,
+                                    int* conts) {
+    UP_REQUIRE(B >= 1 && B <= UP_SERVE_CAP, UP_ERR_INVALID, "%s: %d samples (1..%d)", what, B, (int)UP_SERVE_CAP);
+    UP_REQUIRE(slots >= 1 && slot_host && first_host, UP_ERR_INVALID, "%s: %d slots, a null slot or first table", what, slots);
+    int nf = 0;
+    for (int b = 0; b < B; ++b) {
+        UP_REQUIRE(slot_host[b] >= -1 && slot_host[b] < slots, UP_ERR_INVALID, "%s: slot[%d] = %d outside -1..%d", what, b,
+                   (int)slot_host[b], slots - 1);
+        for (int a = 0; a < b; ++a)
+            UP_REQUIRE(slot_host[b] < 0 || slot_host[a] != slot_host[b], UP_ERR_INVALID, "%s: slot %d named by samples %d and %d", what,
+                       (int)slot_host[b], a, b);
+        nf += slot_host[b] < 0 || first_host[b] != 0;
+    }
+    if (firsts) *firsts = nf;
+    if (conts) *conts = B - nf;
+    return UP_OK;
+}
+
 // ---- bf16 storage (BASELINE configs[4]): activations as raw bf16 bit patterns in HBM, arithmetic in fp32 -------------
 typedef uint16_t bf16_t;          // (element-type codes UP_DT_F32 / UP_DT_BF16: include/unipose_hip.h)
 #ifndef UP_EMU

@@ -1773,6 +1773,57 @@ class LSTMGates(Function):
         return dg, dcp, None
 
 
+def serve_tables(slot, first):
+    """The per-call tables of the stream-serving entries as two host int32 arrays: slot (B,) the pool record of each sample (-1: an
+    idle lane), first (B,) truthy where a stream starts.  The C entries check the values."""
+    slot = [int(s) for s in slot]
+    first = [int(bool(f)) for f in first]
+    if len(slot) != len(first) or not slot:
+        raise ValueError(f"serve_tables: {len(slot)} slots and {len(first)} first flags (one of each per sample)")
+    return (C.c_int32 * len(slot))(*slot), (C.c_int32 * len(first))(*first)
+
+
+def _pool_ok(who, pool):
+    if pool.dim() != 2 or pool.dtype != torch.float32 or not pool.is_contiguous():
+        raise ValueError(f"{who}: the pool is a contiguous float32 (slots, record stride) tensor, got {tuple(pool.shape)} {pool.dtype}")
+    return pool.shape[0], pool.shape[1]
+
+
+def lstm_state_gather(pool: torch.Tensor, slot, first, rows_per_sample: int, ldo: int, dst: torch.Tensor, coff: int = 0):
+    """``up_lstm_state_gather``: lanes [coff, coff + ldo) of every row of `dst` (B * rows_per_sample rows, last dimension the row
+    stride) from the hide rows of a state pool (slots, record stride) float32 — record: hide (rows_per_sample, ldo) then cell —
+    for a continuing sample, +0.0 for a first (`first[b]`) or idle (`slot[b] == -1`) one.  Returns `dst`."""
+    _dev_ok(pool, dst)
+    slots, stride = _pool_ok("lstm_state_gather", pool)
+    st, ft = serve_tables(slot, first)
+    if dst.dtype != torch.float32 or not dst.is_contiguous() or dst.numel() != len(st) * rows_per_sample * dst.shape[-1]:
+        raise ValueError(f"lstm_state_gather: dst {tuple(dst.shape)} {dst.dtype} for {len(st)} samples of {rows_per_sample} rows")
+    _C.check(_C.lib().up_lstm_state_gather(pool.data_ptr(), stride, slots, st, ft, len(st), rows_per_sample, ldo, dst.data_ptr(),
+                                           dst.shape[-1], coff, _stream(dst)), "lstm_state_gather")
+    return dst
+
+
+def lstm_serve_fwd(gates0, gates, pool: torch.Tensor, slot, first, cell: torch.Tensor, hide: torch.Tensor, rows_per_sample: int, cg: int):
+    """``up_lstm_serve_fwd``: the ConvLSTM cell of B samples in different phases.  gates0 (rows, ldg0) the LSTM_0 pre-activations
+    g|i|o, gates (rows, ldg) the LSTM ones g|i|o|f (either may be None when no sample needs it), pool (slots, record stride) the
+    state records, slot / first the call's tables; writes lanes < cg of cell / hide (rows, ldo) and the records of slots >= 0 (their
+    pad lanes as +0.0).  Returns (cell, hide)."""
+    _dev_ok(gates0, gates, pool, cell, hide)
+    slots, stride = _pool_ok("lstm_serve_fwd", pool)
+    st, ft = serve_tables(slot, first)
+    rows = len(st) * rows_per_sample
+    for name, t in (("gates0", gates0), ("gates", gates), ("cell", cell), ("hide", hide)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows * t.shape[-1]):
+            raise ValueError(f"lstm_serve_fwd: {name} {tuple(t.shape)} {t.dtype} for {rows} rows")
+    if cell.shape[-1] != hide.shape[-1]:
+        raise ValueError(f"lstm_serve_fwd: cell rows of {cell.shape[-1]} and hide rows of {hide.shape[-1]} lanes")
+    _C.check(_C.lib().up_lstm_serve_fwd(_ptr(gates0), 0 if gates0 is None else gates0.shape[-1], _ptr(gates),
+                                        0 if gates is None else gates.shape[-1], pool.data_ptr(), stride, slots, st, ft,
+                                        cell.data_ptr(), hide.data_ptr(), cell.shape[-1], len(st), rows_per_sample, cg, _stream(cell)),
+             "lstm_serve_fwd")
+    return cell, hide
+
+
 # --------------------------------------------------------------------------------------------
 # heat-map argmax
 # --------------------------------------------------------------------------------------------

@@ -403,6 +403,9 @@ class UniPoseLSTMPlan(_Plan):
         preds, maxvals, idx = plan.stream(frame, centermap, state, first=True)
         preds, coords, maxvals = plan.clip_frame_final_preds(frames_u8_hwc, center, scale, frame_of=fo)    # the crop and the centre map too
         preds, coords, maxvals = plan.stream_frames(frames_u8_hwc, center, scale, state, first=True)
+        pool = plan.stream_pool(32)                                        # many cameras: a batch whose samples start and restart on their own
+        preds, maxvals, idx = plan.serve(frames, centermaps, pool, slot=[5, -1, 0], first=[1, 0, 0])      # (batch 3; -1: an idle lane)
+        preds, coords, maxvals = plan.serve_frames(frames_u8_hwc, center, scale, pool, slot, first)
 
     The state is the caller's, NCHW (B, K+2, h, w) as the reference's signature has it; the (K+2, h, w) zeros of the reference's
     first call are accepted too (broadcast over the batch like ``unipose._state``, and ignored when ``first`` is set, as the
@@ -707,3 +710,122 @@ class UniPoseLSTMPlan(_Plan):
             self._stream()), "unipose_lstm_stream_frame_final_preds")
         del keep
         return (preds, coords, maxvals) if heat is None else (preds, coords, maxvals, heat)
+
+    # ---- many independent streams in one call: the state in a pool of per-stream records ---------------------------------------------
+    def stream_pool(self, slots: int):
+        """The recurrent state of `slots` streams for ``serve`` / ``serve_frames``: aligned uint8 bytes
+        (``up_unipose_lstm_plan_pool_bytes``), one record per stream — hide (h, w, rup4(K+2)) then cell, float32, the record stride
+        rounded up to 256 bytes (``pool_view``).  The content does not matter: a stream's first frame writes its whole record."""
+        n = _C.lib().up_unipose_lstm_plan_pool_bytes(self._plan, int(slots))
+        if n == 0:
+            raise ValueError(f"UniPoseLSTMPlan.stream_pool: {slots} slots")
+        buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        off = (-buf.data_ptr()) % 256
+        return buf[off:off + n]
+
+    def _pool_slots(self, who, pool):
+        rec = _C.lib().up_unipose_lstm_plan_pool_bytes(self._plan, 1)
+        if (not isinstance(pool, torch.Tensor) or pool.dtype != torch.uint8 or pool.dim() != 1 or pool.numel() < rec or pool.numel() % rec
+                or pool.device != self.device or not pool.is_contiguous() or pool.data_ptr() % 256):
+            raise ValueError(f"UniPoseLSTMPlan.{who}: `pool` is not a buffer of stream_pool() (records of {rec} bytes, uint8, 256-byte "
+                             f"aligned, on {self.device})")
+        return pool.numel() // rec
+
+    def pool_view(self, pool: torch.Tensor):
+        """A float32 view (slots, 2, h, w, rup4(K+2)) of a ``stream_pool()`` buffer: [s, 0] the hidden and [s, 1] the cell state of
+        the stream in slot s, NHWC, the pad lanes zeros."""
+        slots = self._pool_slots("pool_view", pool)
+        h, w, ldo = self.out_height, self.out_width, (self.num_classes + 2 + 3) // 4 * 4
+        return pool.view(torch.float32).view(slots, -1)[:, :2 * h * w * ldo].view(slots, 2, h, w, ldo)
+
+    def _serve_tables(self, who, slot, first):
+        from . import ops
+        if len(slot) != self.batch or len(first) != self.batch:
+            raise ValueError(f"UniPoseLSTMPlan.{who}: {len(slot)} slots and {len(first)} first flags for a batch of {self.batch}")
+        return ops.serve_tables(slot, first)
+
+    def serve(self, frame: torch.Tensor, centermap: torch.Tensor, pool: torch.Tensor, slot, first, full_resolution: bool = False,
+              heat: torch.Tensor = None):
+        """One frame of up to `batch` independent streams in ONE call (``up_unipose_lstm_serve_keypoints``): ``stream`` for a batch
+        whose samples start, continue and restart on their own.  slot (B,): the record of `pool` (``stream_pool(slots)``) that holds
+        sample b's stream, -1 for a lane with no stream (it is computed as a first frame and touches nothing of the pool); first (B,):
+        truthy where the stream starts or restarts with this frame (LSTM_0, its record is not read).  Returns (preds (B, K+1, 2),
+        maxvals (B, K+1, 1), idx (B, K+1) int32): lane b has equal bits to lane b of ``stream`` of the same batch with ``first=True``
+        resp. with that stream's state in lane b, and the record becomes that lane of the new state.  `heat`: an optional
+        (B, K+1, h, w) tensor that receives the NCHW heat-maps."""
+        B, H, W, h, w, K = self.batch, self.height, self.width, self.out_height, self.out_width, self.num_classes
+        x = self._input(frame, (B, 3, H, W), "frame")
+        cm = self._input(centermap, (B, 1, H, W), "centre map")
+        slots = self._pool_slots("serve", pool)
+        st, ft = self._serve_tables("serve", slot, first)
+        if heat is not None:
+            _check_out("UniPoseLSTMPlan.serve", "heat", heat, (B, K + 1, h, w), self.device)
+        preds, maxvals, idx = self._outs("UniPoseLSTMPlan.serve", None, ("preds", "maxvals", "idx"),
+                                         ((B, K + 1, 2), (B, K + 1, 1), (B, K + 1)), (torch.float32, torch.float32, torch.int32))
+        oh, ow = (H, W) if full_resolution else (h, w)
+        ws, nbytes = self._ws(_C.lib().up_unipose_lstm_plan_program_workspace(self._plan, _C.PROGRAM_SERVE))
+        _C.check(_C.lib().up_unipose_lstm_serve_keypoints(self._plan, x.data_ptr(), cm.data_ptr(), pool.data_ptr(), slots, st, ft, oh, ow,
+                                                          idx.data_ptr(), preds.data_ptr(), maxvals.data_ptr(),
+                                                          None if heat is None else heat.data_ptr(), ws, nbytes, self._stream()),
+                 "unipose_lstm_serve_keypoints")
+        return preds, maxvals, idx
+
+    def serve_frames(self, frames: torch.Tensor, center, scale, pool: torch.Tensor, slot, first, frame_of=None, rot=0, valid_hw=None,
+                     crop_center=None, sigma: float = 3.0, res=None, heat: torch.Tensor = None):
+        """One camera frame of up to `batch` independent streams in, joints in frame pixels out
+        (``up_unipose_lstm_serve_frame_final_preds``): ``stream_frames`` with the state in `pool` and the per-sample `slot` / `first`
+        of ``serve``.  Returns (preds (B, K+1, 2) in source-frame pixels, coords (B, K+1, 2), maxvals (B, K+1, 1)) and, where given,
+        `heat` as a fourth item — equal bits to ``serve`` of the cropped frames and ``ops.make_centermaps(crop_center)``, followed by
+        ``ops.final_preds``."""
+        from . import protocol
+        B, h, w, K = self.batch, self.out_height, self.out_width, self.num_classes
+        args, keep, (c, sc) = self._frame_args("serve_frames", frames, center, scale, frame_of, rot, valid_hw)
+        cc = self._crop_center("serve_frames", crop_center, (B,))
+        slots = self._pool_slots("serve_frames", pool)
+        st, ft = self._serve_tables("serve_frames", slot, first)
+        if heat is not None:
+            _check_out("UniPoseLSTMPlan.serve_frames", "heat", heat, (B, K + 1, h, w), self.device)
+        res = [w, h] if res is None else protocol._res(res)
+        if int(res[0]) <= 0 or int(res[1]) <= 0:
+            raise ValueError(f"UniPoseLSTMPlan.serve_frames: res {list(res)}")
+        inv = torch.from_numpy(protocol.inverse_maps(c, sc, res)).to(self.device)
+        preds, coords, maxvals = self._outs("UniPoseLSTMPlan.serve_frames", None, ("preds", "coords", "maxvals"),
+                                            ((B, K + 1, 2), (B, K + 1, 2), (B, K + 1, 1)))
+        ws, nbytes = self._ws(_C.lib().up_unipose_lstm_plan_program_workspace(self._plan, _C.PROGRAM_SERVE + 1))
+        _C.check(_C.lib().up_unipose_lstm_serve_frame_final_preds(
+            self._plan, *args, cc.data_ptr(), float(sigma), pool.data_ptr(), slots, st, ft, inv.data_ptr(), int(res[0]), int(res[1]),
+            preds.data_ptr(), coords.data_ptr(), maxvals.data_ptr(), None if heat is None else heat.data_ptr(), ws, nbytes,
+            self._stream()), "unipose_lstm_serve_frame_final_preds")
+        del keep
+        return (preds, coords, maxvals) if heat is None else (preds, coords, maxvals, heat)
+
+
+class StreamSlots:
+    """A free list over the records of a ``stream_pool(slots)``: ``acquire()`` hands out the lowest free slot when a stream starts,
+    ``release(s)`` takes it back when the stream ends.  Host-only bookkeeping: it touches no device memory (a record needs no
+    clearing: the stream's first frame writes all of it)."""
+
+    def __init__(self, slots: int):
+        if int(slots) < 1:
+            raise ValueError(f"StreamSlots: {slots} slots")
+        self.slots = int(slots)
+        self._free = list(range(self.slots - 1, -1, -1))       # a stack, the lowest slot on top
+        self._used = set()
+
+    def acquire(self) -> int:
+        if not self._free:
+            raise RuntimeError(f"StreamSlots: all {self.slots} slots are in use")
+        s = self._free.pop()
+        self._used.add(s)
+        return s
+
+    def release(self, s: int):
+        if s not in self._used:
+            raise ValueError(f"StreamSlots: slot {s} is not in use")
+        self._used.remove(s)
+        self._free.append(s)
+        self._free.sort(reverse=True)
+
+    @property
+    def free(self) -> int:
+        return len(self._free)
